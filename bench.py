@@ -32,6 +32,7 @@ import torch  # noqa: E402
 HEIGHT, WIDTH, MAX_DISP, ITERS, CLIP_LEN = 480, 640, 192.0, 32, 10
 HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 LOOKUP_BYTES_PER_PIXEL = 308    # 4 levels x 10 taps x 4 B + 4 B coord + 36 x 4 B out
+DUMP_LIMIT_BYTES = 64 * 10**6   # --dump-outputs: all .npy files together stay under this
 
 
 CONTRACTION = ("convolutions: fp16 hi/lo split operands, 3 x v_mfma_f32_32x32x16_f16 per product, fp32 accumulate (error <= fp32 MFMA "
@@ -99,6 +100,31 @@ class ClipRunner:
         if self.t == 0:
             self.state = None
         return out
+
+
+def dump_outputs(dirname, out, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: what the caller of the timed path received from its last timed step (TCStereo.forward's test-mode dict), one
+    float32 DIR/<name>.npy per array.  When the arrays together exceed `limit` bytes, each is replaced by a seeded sample of its
+    flattened elements (sorted indices, drawn from `seed` and the array's size only), so two builds run with the same arguments still
+    compare element for element.  Returns the `dump_outputs` object of the result line."""
+    arrays = {"flow": out["flow"], "flow_q": out["flow_q"], "fmap1": out["fmap1"]}
+    arrays.update({f"net_list_{i}": t for i, t in enumerate(out["net_list"])})
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    budget = limit - 1024 * len(arrays)            # (room for the .npy headers)
+    sampled = total > budget
+    os.makedirs(dirname, exist_ok=True)
+    files = {}
+    for name, arr in arrays.items():
+        entry = {"shape": list(arr.shape)}
+        if sampled:
+            k = max(1, arr.size * budget // total)
+            idx = np.sort(np.random.default_rng(seed).choice(arr.size, size=k, replace=False))
+            arr = arr.reshape(-1)[idx]
+            entry["sample"] = int(k)
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(arr, dtype=np.float32))
+        files[name] = entry
+    return {"dir": dirname, "dtype": "float32", "sampled": sampled, "arrays": files}
 
 
 def _quarter(n):
@@ -395,7 +421,13 @@ def main():
                          "no CPU baseline, no extra legs")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher rehearsal without a GPU: ranks, rendezvous, barrier and the statistics gather only (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (flow, flow_q, fmap1, net_list_<i>) as float32 "
+                         "DIR/<name>.npy, rank 0 only; a seeded sample of each array when they exceed 64 MB together.  fmap1 and frame 0 of "
+                         "the clip are bit-reproducible run to run; later frames are not (the splat's float atomics, DESIGN.md section 7)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.quick:
         a.no_cpu_baseline, a.batched_leg, a.drop_in_steps, a.kitti_steps = True, 0, 0, 0
@@ -449,6 +481,8 @@ def main():
         tdist.barrier()
         elapsed = time.perf_counter() - t0
         per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps))
+    # outside the timed region, before anything else runs on the model
+    dumped = dump_outputs(a.dump_outputs, runner.last) if a.dump_outputs and rank == 0 else None
     # the device-side replacement of the reference's NaN asserts (update.py:27-35,58-67,78-86,155-158): a timed frame whose
     # activations left the S16 domain (bit 0: clamped at 65504, bit 1: NaN / Inf) was timed on garbage — no headline for it
     domain_flags = s16.take_flags()
@@ -664,7 +698,7 @@ def main():
             "domain_flags": all_flags,
             "gathered_eval_vs_synthetic_gt": {k: (round(v, 4) if isinstance(v, float) else v) for k, v in gathered_eval.items()},
             "roofline": roof, "cpu_baseline": cpu, "epe_vs_oracle_first_frames": epe_vs_oracle, "batched_leg": batched,
-            "prefetch_leg": drop_in, "kitti_leg": kitti, "tartanair_leg": real,
+            "prefetch_leg": drop_in, "kitti_leg": kitti, "tartanair_leg": real, "dump_outputs": dumped,
             "ranks_frames": [int(v[0]) for v in vecs],
             "dist_world_size": torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1,
             "dist_backend": torch.distributed.get_backend() if torch.distributed.is_initialized() else None,

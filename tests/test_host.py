@@ -344,6 +344,34 @@ def test_formats_match_reference_fixtures(tmp_path):
     assert img.dtype == np.float32 and np.array_equal(img, g["png_out"])
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: every array of the forward() dict as float32 <name>.npy; above the size limit, the same seeded
+    sample of each array on every run, and the files together stay under the limit.  --steps below 1 is refused."""
+    sys.path.insert(0, ROOT)
+    import bench
+    gen = torch.Generator().manual_seed(3)
+    out = {"flow": torch.randn(2, 1, 64, 96, generator=gen), "flow_q": torch.randn(2, 1, 16, 24, generator=gen),
+           "fmap1": torch.randn(2, 256, 16, 24, generator=gen).double(),
+           "net_list": [torch.randn(2, 128, 16, 24, generator=gen), torch.randn(2, 128, 8, 12, generator=gen), torch.randn(2, 128, 4, 6, generator=gen)]}
+    names = ["flow", "flow_q", "fmap1", "net_list_0", "net_list_1", "net_list_2"]
+    full = bench.dump_outputs(str(tmp_path / "full"), out)
+    assert not full["sampled"] and sorted(full["arrays"]) == sorted(names)
+    for n in names:
+        a = np.load(tmp_path / "full" / f"{n}.npy")
+        want = out[n] if n in out else out["net_list"][int(n[-1])]
+        assert a.dtype == np.float32 and a.shape == tuple(want.shape) and np.array_equal(a, want.float().numpy()), n
+    limit = 200_000
+    runs = [bench.dump_outputs(str(tmp_path / d), out, limit=limit) for d in ("s1", "s2")]
+    assert runs[0]["sampled"] and runs[0] == dict(runs[1], dir=runs[0]["dir"])
+    assert sum(os.path.getsize(tmp_path / "s1" / f"{n}.npy") for n in names) <= limit
+    for n in names:
+        a, b = np.load(tmp_path / "s1" / f"{n}.npy"), np.load(tmp_path / "s2" / f"{n}.npy")
+        assert a.dtype == np.float32 and a.ndim == 1 and a.size == runs[0]["arrays"][n]["sample"] and np.array_equal(a, b), n
+        assert np.isin(a, np.load(tmp_path / "full" / f"{n}.npy")).all(), n
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--dry-run"], capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
 def test_gpu_count_from_kfd_topology(tmp_path, monkeypatch):
     """bench.py's launcher counts GPUs from the KFD topology in sysfs (no HIP / amdsmi call in the parent of the ranks)."""
     sys.path.insert(0, ROOT)
