@@ -35,7 +35,8 @@ extern "C" {
 
 typedef void* tcs_stream_t;
 
-int tcs_abi_version(void);                 /* bumped when a signature changes (7: grouped launches, blend_warm_*) */
+int tcs_abi_version(void);                 /* bumped when a signature changes (7: grouped launches, blend_warm_*; 8: `products`, the
+                                              last field of tcs_conv_desc and tcs_conv_s16_desc) */
 const char* tcs_error_string(int code);
 
 /* ------------------------------------------------------------------------------------------------
@@ -249,6 +250,11 @@ typedef struct tcs_conv_desc {
     int in_transform;
     const float* src_batch2;
     int batch_split;
+    /* MFMA products per (16-channel k-step, tap) of TCS_MATH_F16X3: 0 or 3 = the fp16-split contraction (a_lo.b_hi + a_hi.b_lo +
+     * a_hi.b_hi, fp32-grade; the default); 1 = a_hi.b_hi only: sum f16(x) * f16(w * 2^s) * 2^-s with fp32 accumulation (the opt-in fp16
+     * mode of the Python layer).  Storage, epilogues and the domain guard are the same in both.  Any other value, and 1 with
+     * TCS_MATH_F32, is TCS_EINVAL. */
+    int products;
 } tcs_conv_desc;
 
 /* packed weight size in floats for a [Cout,Cin,k,k] convolution */
@@ -396,6 +402,11 @@ typedef struct tcs_conv_s16_desc {
      * its duration.  No effect on any result.  NULL = off. */
     const float* blend_warm_pyr[4];
     int blend_warm_radius;
+    /* MFMA products per (k-step, tap): 0 or 3 = the fp16-split contraction (default); 1 = hi halves only, f16(x) . f16(w * 2^s) * 2^-s
+     * with fp32 accumulation: the stage stages the hi plane of the inputs and the hi weight pieces only (as tcs_conv_desc.products).
+     * The tap-partial fold (tap_*) stays a 3-product contraction.  tcs_conv2d_s16_group fuses two descriptors only when their counts
+     * match.  Any other value is TCS_EINVAL. */
+    int products;
 } tcs_conv_s16_desc;
 
 /* S16 glue of the loop: pool2x / interp (core/update.py:114-124), the up-blocks' InstanceNorm + LeakyReLU + skip

@@ -37,9 +37,22 @@ class autocast(contextlib.AbstractContextManager):
         return False
 
 
+# Arithmetic of the fp16-split convolutions per model instance (`args.hip_precision`, DESIGN.md section 5 / INTEGRATION.md):
+#   "fp32" (default): fp16 hi/lo split operands, three MFMA products each, fp32 accumulation — fp32-grade results;
+#   "fp16": the hi halves only, sum f16(x) * f16(w) with fp32 accumulation, one product (tcs_conv*_desc.products = 1).
+# Storage, epilogues, every non-convolution kernel, the fp32 kernels (correlation, the gradient-candidate stem, the 7x7 stems) and the
+# two small split contractions (fused HiddenstateUpdater, tap partials) are the same in both.  `mixed_precision` / `autocast` do not
+# select it.
+HIP_PRECISIONS = {"fp32": 0, "fp16": 1}
+
+
 class TCStereo(nn.Module):
     def __init__(self, args):
         super().__init__()
+        precision = getattr(args, "hip_precision", "fp32")
+        if precision not in HIP_PRECISIONS:
+            raise ValueError(f"hip_precision must be one of {sorted(HIP_PRECISIONS)}, got {precision!r}")
+        self._hip_precision = precision
         self.args = args
         self.scale_rate = 1 / (2 ** args.n_downsample)
         hd = list(args.hidden_dims)
@@ -59,9 +72,20 @@ class TCStereo(nn.Module):
         self.hiddenstate_update = HiddenstateUpdater(hd[0])
         # one pool of pre-split ("S16") activation buffers for the whole model: allocated (zero-filled) on first use,
         # reused every iteration and frame (tcs_mi355/s16.py)
-        pool = s16.S16Pool()
+        pool = s16.S16Pool(products=HIP_PRECISIONS[precision])
         for m in self.modules():
             m._s16pool = pool
+        # layers that stay fp16-split in both modes: the fused HiddenstateUpdater and the 3x3 convolutions to 1-2 channels that run folded
+        # into their producer as tap partials (core/update.py: products_of)
+        for m in self.hiddenstate_update.modules():
+            m._tcs_x3 = True
+        self.update_block.flow_head.conv2._tcs_x3 = True
+        self.disp_grad_refine.residual_head[2]._tcs_x3 = True
+
+    @property
+    def hip_precision(self) -> str:
+        """"fp32" or "fp16": the arithmetic of this model's fp16-split convolutions, fixed at construction (args.hip_precision)."""
+        return self._hip_precision
 
     def freeze_bn(self):
         for m in self.modules():

@@ -34,24 +34,36 @@ from tcs_mi355.streams import fork_join
 CONV_MATH = "f16x3"
 
 
+def products_of(conv: nn.Module) -> int:
+    """MFMA products per k-step of a layer's fp16-split contraction (tcs_conv*_desc.products): its model's setting (S16Pool.products,
+    TCStereo's hip_precision: 1 for "fp16", 0 = fp16-split), except for layers marked `_tcs_x3`, which stay fp16-split in every
+    mode (the fused HiddenstateUpdater and the convolutions folded into their producer as tap partials)."""
+    if getattr(conv, "_tcs_x3", False):
+        return 0
+    pool = getattr(conv, "_s16pool", None)
+    return 0 if pool is None else pool.products
+
+
 def packed(conv: nn.Conv2d) -> ops.PackedConv:
     w, b = conv.weight, conv.bias
     math = getattr(conv, "_tcs_math", None) or CONV_MATH
     if conv.stride == (2, 2):
         math = "f16x3"          # stride-2 convolutions exist on the fp16-split kernel only
-    key = (w.data_ptr(), w._version, w.device, None if b is None else (b.data_ptr(), b._version), math)
+    nprod = products_of(conv) if math == "f16x3" else 0
+    key = (w.data_ptr(), w._version, w.device, None if b is None else (b.data_ptr(), b._version), math, nprod)
     hit = getattr(conv, "_tcs_packed", None)
     if hit is None or hit[0] != key:
         if conv.stride not in ((1, 1), (2, 2)) or conv.dilation != (1, 1) or conv.groups != 1 or \
                 conv.padding != (conv.kernel_size[0] // 2,) * 2:
             raise NotImplementedError(f"tcs_conv2d covers stride-1/2 'same'-padded convolutions, got {conv}")
-        hit = (key, ops.pack_conv(w, b, math))
+        hit = (key, ops.pack_conv(w, b, math, nprod))
         conv._tcs_packed = hit
     return hit[1]
 
 
 def packed16(conv: nn.Conv2d) -> ops.PackedConv:
-    """fp16-split packing also for a layer pinned to fp32 MFMA on its fp32-tensor path: the S16 kernels contract fp16 halves by construction."""
+    """fp16-split packing also for a layer pinned to fp32 MFMA on its fp32-tensor path: the S16 kernels contract fp16 halves by construction.
+    A pinned layer keeps the 3-product contraction in every precision mode."""
     if getattr(conv, "_tcs_math", None) == "f32":
         w, b = conv.weight, conv.bias
         key = (w.data_ptr(), w._version, w.device, None if b is None else (b.data_ptr(), b._version))
@@ -68,13 +80,14 @@ def packed16_part(conv: nn.Conv2d, cin_slices, with_bias: bool = True) -> ops.Pa
     convolution is linear in its input channels, so a layer over cat(a, b) whose inputs are ready at different times runs as
     conv_a(a) + bias -> fp32 partial sum, then conv_b(b) with that sum as the epilogue's addend (tcs_mi355.h, addend_ctot)."""
     w, b = conv.weight, conv.bias
-    key = (w.data_ptr(), w._version, w.device, None if b is None else (b.data_ptr(), b._version))
+    nprod = products_of(conv)
+    key = (w.data_ptr(), w._version, w.device, None if b is None else (b.data_ptr(), b._version), nprod)
     cache = conv.__dict__.setdefault("_tcs_parts", {})
     spec = (tuple(tuple(int(v) for v in sl) for sl in cin_slices), bool(with_bias))
     hit = cache.get(spec)
     if hit is None or hit[0] != key:
         ws = torch.cat([w.detach()[:, lo:hi] for lo, hi in spec[0]], 1).contiguous()
-        hit = (key, ops.pack_conv(ws, b if with_bias else None, "f16x3"))
+        hit = (key, ops.pack_conv(ws, b if with_bias else None, "f16x3", nprod))
         cache[spec] = hit
     return hit[1]
 
@@ -82,7 +95,8 @@ def packed16_part(conv: nn.Conv2d, cin_slices, with_bias: bool = True) -> ops.Pa
 def packed16_cat(convs) -> ops.PackedConv:
     """fp16-split packing of several layers that read the same input, concatenated along Cout (weights and biases): one
     launch, the outputs split again by channel range in the epilogue (tcs_conv_s16_desc.out16b)."""
-    key = tuple((c.weight.data_ptr(), c.weight._version, None if c.bias is None else (c.bias.data_ptr(), c.bias._version)) for c in convs)
+    nprod = products_of(convs[0])
+    key = tuple((c.weight.data_ptr(), c.weight._version, None if c.bias is None else (c.bias.data_ptr(), c.bias._version)) for c in convs) + (nprod,)
     host = convs[0]
     cache = host.__dict__.setdefault("_tcs_cat", {})
     ids = tuple(id(c) for c in convs)
@@ -90,7 +104,7 @@ def packed16_cat(convs) -> ops.PackedConv:
     if hit is None or hit[0] != key:
         w = torch.cat([c.weight.detach() for c in convs], 0).contiguous()
         b = torch.cat([(c.bias.detach() if c.bias is not None else torch.zeros(c.out_channels, device=c.weight.device)) for c in convs], 0).contiguous()
-        hit = (key, ops.pack_conv(w, b, "f16x3"))
+        hit = (key, ops.pack_conv(w, b, "f16x3", nprod))
         cache[ids] = hit
     return hit[1]
 
@@ -204,12 +218,13 @@ def hip_conv(conv, srcs, act="none", **kw):
 
 def packed_deconv(deconv: nn.ConvTranspose2d) -> ops.PackedConv:
     w = deconv.weight
-    key = (w.data_ptr(), w._version, w.device)
+    nprod = products_of(deconv)
+    key = (w.data_ptr(), w._version, w.device, nprod)
     hit = getattr(deconv, "_tcs_packed", None)
     if hit is None or hit[0] != key:
         if deconv.kernel_size != (4, 4) or deconv.stride != (2, 2) or deconv.padding != (1, 1) or deconv.bias is not None:
             raise NotImplementedError(f"tcs deconv covers ConvTranspose2d(4, stride 2, pad 1, bias=False), got {deconv}")
-        hit = (key, ops.pack_deconv4x4s2(w))
+        hit = (key, ops.pack_deconv4x4s2(w, nprod))
         deconv._tcs_packed = hit
     return hit[1]
 

@@ -368,6 +368,8 @@ int tcs_conv2d(const tcs_conv_desc* d, tcs_stream_t stream) {
         return TCS_EINVAL;
     if (!d->out && d->epilogue != TCS_EPI_LINEAR) return TCS_EINVAL;
     if (d->n_src < 1 || d->n_src > TCS_MAX_SRC) return TCS_EINVAL;
+    const int nprod = d->products == 0 ? 3 : d->products;          // 0 (zero-filled descriptor) = the fp16-split contraction
+    if ((nprod != 1 && nprod != 3) || (nprod == 1 && d->math != TCS_MATH_F16X3)) return TCS_EINVAL;
     if (d->B <= 0 || d->B > 65535 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0) return TCS_EINVAL;
     ConvArgs a;
     int tot = 0;
@@ -419,7 +421,7 @@ int tcs_conv2d(const tcs_conv_desc* d, tcs_stream_t stream) {
         a.w_unscale = d->weight_unscale;
         a.w_bytes = (int)(tcs_conv_packed_floats_f16x3(d->Cout, d->Cin, d->ksize) * sizeof(float));
         a.npx = tcs_cdiv(a.W, 32);
-        return tcs_conv_f16x3_launch(a, d->ksize, d->epilogue, stride, s);
+        return tcs_conv_f16x3_launch(a, d->ksize, d->epilogue, stride, nprod, s);
     }
     if (d->math != TCS_MATH_F32) return TCS_EINVAL;
     if (stride != 1 || d->epilogue == TCS_EPI_DECONV2X) return TCS_EUNSUPPORTED;      // fp32 kernel: stride-1 'same' only

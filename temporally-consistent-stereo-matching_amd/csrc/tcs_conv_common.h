@@ -182,4 +182,4 @@ __device__ __forceinline__ void conv_epilogue_tile(const ConvArgs& a, int b, int
     }
 }
 
-int tcs_conv_f16x3_launch(ConvArgs& a, int ksize, int epilogue, int stride, hipStream_t s);   // tcs_conv_f16.hip
+int tcs_conv_f16x3_launch(ConvArgs& a, int ksize, int epilogue, int stride, int nprod, hipStream_t s);   // nprod: 1 or 3 products per k-step   // tcs_conv_f16.hip

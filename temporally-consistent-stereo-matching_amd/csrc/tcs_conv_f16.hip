@@ -56,8 +56,12 @@ __device__ __forceinline__ void split_f16x2(float x0, float x1, half2_t& hi, hal
 // ROWS = waves along the patch rows (patch = ROWS*MP rows): 5 instead of 4 turns the 600- and 300-workgroup grids of the
 // 1/4-scale layers (2.3 and 1.2 workgroups per CU: some CUs carry one more than the others for the whole kernel) into
 // 480 and 240 (at most 2 / 1 per CU).
-template <int KS, int MT, int MP, int KSTEPS, int EPI, int STRIDE = 1, int ROWS = 4>
-__global__ __launch_bounds__(64 * ROWS) void k_conv_f16x3(ConvArgs a) {
+// NPR = MFMA products per (k-step, tap): 3 = the fp16-split contraction above (k_conv_f16x3*); 1 = a_hi.b_hi only
+// (tcs_conv_desc.products = 1; k_conv_f16x1*): f16(x) . f16(w 2^s) with fp32 accumulation — the lo halves are neither stored to LDS
+// nor fetched.  Same tiles, same LDS image, same epilogues.
+template <int KS, int MT, int MP, int KSTEPS, int EPI, int STRIDE = 1, int ROWS = 4, int NPR = 3>
+__device__ __forceinline__ void f16_conv_body(const ConvArgs& a) {
+    static_assert(NPR == 1 || NPR == 3, "products per k-step: 1 or 3");
     constexpr int NTHREADS = 64 * ROWS, MTB = MT;                         // MTB: cout tiles per block
     constexpr int HALO = KS / 2, PR = ROWS * MP, IH = STRIDE * PR + KS - STRIDE, IW = STRIDE * 32 + KS - STRIDE, TAPS = KS * KS,
                   IN_CH = IH * IW;
@@ -176,7 +180,7 @@ __global__ __launch_bounds__(64 * ROWS) void k_conv_f16x3(ConvArgs a) {
                     }                                                                                       \
                     const size_t unit = (size_t)grp * IN_CH + tpos + TPP * k;                               \
                     *reinterpret_cast<half8*>(s_in_hi + unit * 16) = hi8;                                   \
-                    *reinterpret_cast<half8*>(s_in_lo + unit * 16) = lo8;                                   \
+                    if constexpr (NPR == 3) *reinterpret_cast<half8*>(s_in_lo + unit * 16) = lo8;           \
                 }                                                                                           \
             }                                                                                               \
         }                                                                                                   \
@@ -194,19 +198,21 @@ __global__ __launch_bounds__(64 * ROWS) void k_conv_f16x3(ConvArgs a) {
         _Pragma("unroll") for (int p = 0; p < MP; ++p) {                                                    \
             const size_t boff = ((size_t)(2 * (KSI) + half) * IN_CH + (STRIDE * (wave * MP + p) + dy_) * IW + dx_ + STRIDE * l31) * 16; \
             F.b_hi[p] = *reinterpret_cast<const half8*>(s_in_hi + boff);                                    \
-            F.b_lo[p] = *reinterpret_cast<const half8*>(s_in_lo + boff);                                    \
+            if constexpr (NPR == 3) F.b_lo[p] = *reinterpret_cast<const half8*>(s_in_lo + boff);            \
         }                                                                                                   \
         _Pragma("unroll") for (int m = 0; m < MT; ++m) {                                                    \
             const unsigned char* wt = s_w + ((size_t)(((KSI) * TAPS + (T)) * MTB + wave_g * MT + m) * 128 + lane) * 16; \
             F.a_hi[m] = *reinterpret_cast<const half8*>(wt);                                                \
-            F.a_lo[m] = *reinterpret_cast<const half8*>(wt + 1024);                                         \
+            if constexpr (NPR == 3) F.a_lo[m] = *reinterpret_cast<const half8*>(wt + 1024);                 \
         }                                                                                                   \
     }
 #define TCS_MMA(F)                                                                                          \
     _Pragma("unroll") for (int m = 0; m < MT; ++m)                                                          \
         _Pragma("unroll") for (int p = 0; p < MP; ++p) {                                                    \
-            acc[m][p] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.a_lo[m], F.b_hi[p], acc[m][p], 0, 0, 0);   \
-            acc[m][p] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.a_hi[m], F.b_lo[p], acc[m][p], 0, 0, 0);   \
+            if constexpr (NPR == 3) {                                                                       \
+                acc[m][p] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.a_lo[m], F.b_hi[p], acc[m][p], 0, 0, 0); \
+                acc[m][p] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.a_hi[m], F.b_lo[p], acc[m][p], 0, 0, 0); \
+            }                                                                                               \
             acc[m][p] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.a_hi[m], F.b_hi[p], acc[m][p], 0, 0, 0);   \
         }
 
@@ -226,17 +232,18 @@ __global__ __launch_bounds__(64 * ROWS) void k_conv_f16x3(ConvArgs a) {
     {                                                                                                       \
         _Pragma("unroll") for (int p = 0; p < MP; ++p) {                                                    \
             TCS_DSREAD(F.b_hi[p], addr_b, ((2 * (KSI)) * IN_CH + (STRIDE * p + (T) / KS) * IW + (T) % KS) * 16);            \
-            TCS_DSREAD(F.b_lo[p], addr_b, ((2 * (KSI)) * IN_CH + (STRIDE * p + (T) / KS) * IW + (T) % KS) * 16 + IN_BYTES); \
+            if constexpr (NPR == 3)                                                                         \
+                TCS_DSREAD(F.b_lo[p], addr_b, ((2 * (KSI)) * IN_CH + (STRIDE * p + (T) / KS) * IW + (T) % KS) * 16 + IN_BYTES); \
         }                                                                                                   \
         _Pragma("unroll") for (int m = 0; m < MT; ++m) {                                                    \
             TCS_DSREAD(F.a_hi[m], addr_a, (((KSI) * TAPS + (T)) * MTB + m) * 2048);                         \
-            TCS_DSREAD(F.a_lo[m], addr_a, (((KSI) * TAPS + (T)) * MTB + m) * 2048 + 1024);                  \
+            if constexpr (NPR == 3) TCS_DSREAD(F.a_lo[m], addr_a, (((KSI) * TAPS + (T)) * MTB + m) * 2048 + 1024); \
         }                                                                                                   \
     }
 #define TCS_WAIT_LGKM(N) { asm volatile("s_waitcnt lgkmcnt(%0)" :: "i"(N) : "memory"); __builtin_amdgcn_sched_barrier(0); }
 #define TCS_COMPUTE_ASM()                                                                                       \
     {                                                                                                       \
-        constexpr int NSTEP = KSTEPS * TAPS, R = 2 * MP + 2 * MT;                                           \
+        constexpr int NSTEP = KSTEPS * TAPS, R = (NPR == 3 ? 2 : 1) * (MP + MT);                            \
         static_assert(R <= 15, "lgkmcnt field");                                                            \
         Frag f0, f1;                                                                                        \
         TCS_FETCH_ASM(f0, 0, 0)                                                                             \
@@ -351,6 +358,16 @@ __global__ __launch_bounds__(64 * ROWS) void k_conv_f16x3(ConvArgs a) {
     }
 }
 
+template <int KS, int MT, int MP, int KSTEPS, int EPI, int STRIDE = 1, int ROWS = 4>
+__global__ __launch_bounds__(64 * ROWS) void k_conv_f16x3(ConvArgs a) {
+    f16_conv_body<KS, MT, MP, KSTEPS, EPI, STRIDE, ROWS, 3>(a);
+}
+
+template <int KS, int MT, int MP, int KSTEPS, int EPI, int STRIDE = 1, int ROWS = 4>
+__global__ __launch_bounds__(64 * ROWS) void k_conv_f16x1(ConvArgs a) {
+    f16_conv_body<KS, MT, MP, KSTEPS, EPI, STRIDE, ROWS, 1>(a);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Wave-specialised variant: 4 consumer waves (MFMA only) + NP producer waves (global loads, fp16 split, LDS stores) per
 // block, two LDS buffers, ONE barrier per chunk.  In k_conv_f16x3 every wave does all of a chunk's work in sequence
@@ -359,8 +376,8 @@ __global__ __launch_bounds__(64 * ROWS) void k_conv_f16x3(ConvArgs a) {
 // phases in lock step, so the phases add instead of overlapping.  Here the staging of chunk i+1 runs on other waves of
 // the same SIMDs while chunk i is multiplied, and a chunk costs max(MFMA, staging) instead of their sum.
 // Same tiling, LDS images and packed weights as k_conv_f16x3<KS, MT, 1, KSTEPS, EPI>; stride 1 only.
-template <int KS, int MT, int KSTEPS, int EPI, int NP>
-__global__ __launch_bounds__(256 + 64 * NP) void k_conv_f16x3_ws(ConvArgs a) {
+template <int KS, int MT, int KSTEPS, int EPI, int NP, int NPR = 3>
+__device__ __forceinline__ void f16_conv_ws_body(const ConvArgs& a) {
     constexpr int HALO = KS / 2, IH = 4 + KS - 1, IW = 32 + KS - 1, TAPS = KS * KS, IN_CH = IH * IW;
     constexpr int NT = 32 * MT, KC = 16 * KSTEPS, NG = 2 * KSTEPS;
     constexpr int IN_BYTES = NG * IN_CH * 16;                                  // one of {hi, lo}
@@ -459,7 +476,7 @@ __global__ __launch_bounds__(256 + 64 * NP) void k_conv_f16x3_ws(ConvArgs a) {
                     }                                                                                       \
                     const size_t unit = (size_t)grp * IN_CH + tpos + TPP * k;                               \
                     *reinterpret_cast<half8*>(s_in_hi + unit * 16) = hi8;                                   \
-                    *reinterpret_cast<half8*>(s_in_lo + unit * 16) = lo8;                                   \
+                    if constexpr (NPR == 3) *reinterpret_cast<half8*>(s_in_lo + unit * 16) = lo8;           \
                 }                                                                                           \
             }                                                                                               \
         }                                                                                                   \
@@ -510,24 +527,26 @@ __global__ __launch_bounds__(256 + 64 * NP) void k_conv_f16x3_ws(ConvArgs a) {
 #define WS_FETCH(F, KSI, T)                                                                                 \
     {                                                                                                       \
         WS_DSREAD(F.b_hi, addr_b, ((2 * (KSI)) * IN_CH + ((T) / KS) * IW + (T) % KS) * 16);                 \
-        WS_DSREAD(F.b_lo, addr_b, ((2 * (KSI)) * IN_CH + ((T) / KS) * IW + (T) % KS) * 16 + IN_BYTES);      \
+        if constexpr (NPR == 3) WS_DSREAD(F.b_lo, addr_b, ((2 * (KSI)) * IN_CH + ((T) / KS) * IW + (T) % KS) * 16 + IN_BYTES); \
         _Pragma("unroll") for (int m = 0; m < MT; ++m) {                                                    \
             WS_DSREAD(F.a_hi[m], addr_a, (((KSI) * TAPS + (T)) * MT + m) * 2048);                           \
-            WS_DSREAD(F.a_lo[m], addr_a, (((KSI) * TAPS + (T)) * MT + m) * 2048 + 1024);                    \
+            if constexpr (NPR == 3) WS_DSREAD(F.a_lo[m], addr_a, (((KSI) * TAPS + (T)) * MT + m) * 2048 + 1024); \
         }                                                                                                   \
     }
 #define WS_WAIT(N) { asm volatile("s_waitcnt lgkmcnt(%0)" :: "i"(N) : "memory"); __builtin_amdgcn_sched_barrier(0); }
 #define WS_MMA(F)                                                                                           \
     _Pragma("unroll") for (int m = 0; m < MT; ++m) {                                                        \
-        acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.a_lo[m], F.b_hi, acc[m], 0, 0, 0);                \
-        acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.a_hi[m], F.b_lo, acc[m], 0, 0, 0);                \
+        if constexpr (NPR == 3) {                                                                           \
+            acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.a_lo[m], F.b_hi, acc[m], 0, 0, 0);            \
+            acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.a_hi[m], F.b_lo, acc[m], 0, 0, 0);            \
+        }                                                                                                   \
         acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.a_hi[m], F.b_hi, acc[m], 0, 0, 0);                \
     }
     __syncthreads();                                              // chunk 0 is in buffer 0
     for (int i = 0; i < nchunks; ++i) {
         const unsigned boff = (i & 1) ? (unsigned)BUF_BYTES : 0u;
         const unsigned addr_b = addr_b0 + boff, addr_a = addr_a0 + boff;
-        constexpr int NSTEP = KSTEPS * TAPS, R = 2 + 2 * MT;
+        constexpr int NSTEP = KSTEPS * TAPS, R = (NPR == 3 ? 2 : 1) * (1 + MT);
         Frag f0, f1;
         WS_FETCH(f0, 0, 0)
 #pragma unroll
@@ -550,6 +569,16 @@ __global__ __launch_bounds__(256 + 64 * NP) void k_conv_f16x3_ws(ConvArgs a) {
     const size_t pix = (size_t)py * W + px;
 #pragma unroll
     for (int m = 0; m < MT; ++m) conv_epilogue_tile<EPI>(a, b, ct * NT + m * 32 + 4 * half, pix, HW, acc[m], a.w_unscale);
+}
+
+template <int KS, int MT, int KSTEPS, int EPI, int NP>
+__global__ __launch_bounds__(256 + 64 * NP) void k_conv_f16x3_ws(ConvArgs a) {
+    f16_conv_ws_body<KS, MT, KSTEPS, EPI, NP, 3>(a);
+}
+
+template <int KS, int MT, int KSTEPS, int EPI, int NP>
+__global__ __launch_bounds__(256 + 64 * NP) void k_conv_f16x1_ws(ConvArgs a) {
+    f16_conv_ws_body<KS, MT, KSTEPS, EPI, NP, 1>(a);
 }
 
 // OIHW fp32 weights -> the LDS image order, split into (hi, lo) halves after scaling by 2^scale_log2.
@@ -578,11 +607,11 @@ __global__ __launch_bounds__(256) void k_pack_weight_f16x3(const float* __restri
     packed[u] = *reinterpret_cast<uint4*>(&v);
 }
 
-template <int KS, int MT, int MP, int KSTEPS, int EPI, int STRIDE = 1, int ROWS = 4>
+template <int NPR, int KS, int MT, int MP, int KSTEPS, int EPI, int STRIDE = 1, int ROWS = 4>
 static int launch_f16(ConvArgs& a, hipStream_t s) {
     constexpr int IH = STRIDE * ROWS * MP + KS - STRIDE, IW = STRIDE * 32 + KS - STRIDE, TAPS = KS * KS;
     const size_t lds = (size_t)2 * (2 * KSTEPS) * IH * IW * 16 + (size_t)KSTEPS * TAPS * MT * 2 * 1024;
-    auto kern = k_conv_f16x3<KS, MT, MP, KSTEPS, EPI, STRIDE, ROWS>;
+    auto kern = NPR == 3 ? k_conv_f16x3<KS, MT, MP, KSTEPS, EPI, STRIDE, ROWS> : k_conv_f16x1<KS, MT, MP, KSTEPS, EPI, STRIDE, ROWS>;
     if (lds > 64 * 1024) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return TCS_ELAUNCH;
@@ -593,11 +622,11 @@ static int launch_f16(ConvArgs& a, hipStream_t s) {
     return tcs_launch_status();
 }
 
-template <int KS, int MT, int KSTEPS, int EPI, int NP>
+template <int NPR, int KS, int MT, int KSTEPS, int EPI, int NP>
 static int launch_f16_ws(ConvArgs& a, hipStream_t s) {
     constexpr int IH = 4 + KS - 1, IW = 32 + KS - 1, TAPS = KS * KS;
     const size_t lds = 2 * ((size_t)2 * (2 * KSTEPS) * IH * IW * 16 + (size_t)KSTEPS * TAPS * MT * 2 * 1024);
-    auto kern = k_conv_f16x3_ws<KS, MT, KSTEPS, EPI, NP>;
+    auto kern = NPR == 3 ? k_conv_f16x3_ws<KS, MT, KSTEPS, EPI, NP> : k_conv_f16x1_ws<KS, MT, KSTEPS, EPI, NP>;
     if (lds > 64 * 1024) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return TCS_ELAUNCH;
@@ -608,7 +637,7 @@ static int launch_f16_ws(ConvArgs& a, hipStream_t s) {
     return tcs_launch_status();
 }
 
-template <int KS, int EPI>
+template <int NPR, int KS, int EPI>
 static int launch_f16_tile(ConvArgs& a, hipStream_t s) {
     // Tile choice by grid size only (no environment knobs: the library keeps no mutable global state).
     const int nct32 = a.CoutPad / 32;
@@ -621,43 +650,48 @@ static int launch_f16_tile(ConvArgs& a, hipStream_t s) {
         // 64-channel tiles lose 20 % (gru08.zr 135 -> 163 us), so this is limited to MT = 1.
         const long long wg4 = (long long)a.npx * tcs_cdiv(a.H, 4) * a.B * (nct32 / mt), wg5 = (long long)a.npx * tcs_cdiv(a.H, 5) * a.B * (nct32 / mt);
         const double e4 = (double)wg4 / (256.0 * ((wg4 + 255) / 256)), e5 = (double)wg5 / (256.0 * ((wg5 + 255) / 256));
-        if (mt == 1 && e5 > e4 + 0.05 && wg4 > 400 && wg4 <= 768) return launch_f16<3, 1, 1, 1, EPI, 1, 5>(a, s);
+        if (mt == 1 && e5 > e4 + 0.05 && wg4 > 400 && wg4 <= 768) return launch_f16<NPR, 3, 1, 1, 1, EPI, 1, 5>(a, s);
         // Wave-specialised kernel (k_conv_f16x3_ws) for the layers that cannot fill the chip: with <= 1-2 blocks per CU the
         // per-chunk latency chain of the plain kernel is exposed, and overlapping staging with the MFMAs gains 10-18 %
         // (tools/bench_conv.py: 128->128 at 1/32 scale 15.9 -> 13.5 us, gru16.zr 57.6 -> 50.9 us); on full grids it ties or loses.
         const long long blocks_mt1 = px_tiles * nct32;
-        if (blocks_mt1 <= 200) return launch_f16_ws<3, 1, 1, EPI, 8>(a, s);
-        if (blocks_mt1 <= 400) return launch_f16_ws<3, 1, 1, EPI, 4>(a, s);
-        return mt == 2 ? launch_f16<3, 2, 1, 1, EPI>(a, s) : launch_f16<3, 1, 1, 1, EPI>(a, s);
+        if (blocks_mt1 <= 200) return launch_f16_ws<NPR, 3, 1, 1, EPI, 8>(a, s);
+        if (blocks_mt1 <= 400) return launch_f16_ws<NPR, 3, 1, 1, EPI, 4>(a, s);
+        return mt == 2 ? launch_f16<NPR, 3, 2, 1, 1, EPI>(a, s) : launch_f16<NPR, 3, 1, 1, 1, EPI>(a, s);
     }
-    return mt == 2 ? launch_f16<1, 2, 1, 4, EPI>(a, s) : launch_f16<1, 1, 1, 4, EPI>(a, s);
+    return mt == 2 ? launch_f16<NPR, 1, 2, 1, 4, EPI>(a, s) : launch_f16<NPR, 1, 1, 1, 4, EPI>(a, s);
 }
 
-template <int EPI>
+template <int NPR, int EPI>
 static int launch_f16_ks(ConvArgs& a, int ksize, hipStream_t s) {
-    if (ksize == 3) return launch_f16_tile<3, EPI>(a, s);
-    if (ksize == 1) return launch_f16_tile<1, EPI>(a, s);
+    if (ksize == 3) return launch_f16_tile<NPR, 3, EPI>(a, s);
+    if (ksize == 1) return launch_f16_tile<NPR, 1, EPI>(a, s);
     return TCS_EUNSUPPORTED;
 }
 
-int tcs_conv_f16x3_launch(ConvArgs& a, int ksize, int epilogue, int stride, hipStream_t s) {
+template <int NPR>
+static int launch_f16_any(ConvArgs& a, int ksize, int epilogue, int stride, hipStream_t s) {
     a.src_align8 = (a.Cin % 8 == 0) ? 1 : 0;
     for (int i = 0; i < TCS_MAX_SRC; ++i)
         if (a.src_end[i] != 0x7fffffff && (a.src_end[i] % 8) != 0) a.src_align8 = 0;
     if (stride == 2) {                       // 3x3 stride-2 pad-1 (conv_4_8 / conv_8_16 of the U-Nets), linear epilogue
         if (ksize != 3 || epilogue != TCS_EPI_LINEAR) return TCS_EUNSUPPORTED;
-        return launch_f16<3, 1, 1, 1, TCS_EPI_LINEAR, 2>(a, s);
+        return launch_f16<NPR, 3, 1, 1, 1, TCS_EPI_LINEAR, 2>(a, s);
     }
     if (epilogue == TCS_EPI_DECONV2X) {
         if (ksize != 3) return TCS_EUNSUPPORTED;
-        return launch_f16<3, 1, 1, 1, TCS_EPI_DECONV2X, 1>(a, s);
+        return launch_f16<NPR, 3, 1, 1, 1, TCS_EPI_DECONV2X, 1>(a, s);
     }
     switch (epilogue) {
-        case TCS_EPI_LINEAR: return launch_f16_ks<TCS_EPI_LINEAR>(a, ksize, s);
-        case TCS_EPI_GRU_ZR: return launch_f16_ks<TCS_EPI_GRU_ZR>(a, ksize, s);
-        case TCS_EPI_GRU_Q: return launch_f16_ks<TCS_EPI_GRU_Q>(a, ksize, s);
+        case TCS_EPI_LINEAR: return launch_f16_ks<NPR, TCS_EPI_LINEAR>(a, ksize, s);
+        case TCS_EPI_GRU_ZR: return launch_f16_ks<NPR, TCS_EPI_GRU_ZR>(a, ksize, s);
+        case TCS_EPI_GRU_Q: return launch_f16_ks<NPR, TCS_EPI_GRU_Q>(a, ksize, s);
         default: return TCS_EINVAL;
     }
+}
+
+int tcs_conv_f16x3_launch(ConvArgs& a, int ksize, int epilogue, int stride, int nprod, hipStream_t s) {
+    return nprod == 1 ? launch_f16_any<1>(a, ksize, epilogue, stride, s) : launch_f16_any<3>(a, ksize, epilogue, stride, s);
 }
 
 extern "C" size_t tcs_conv_packed_floats_f16x3(int Cout, int Cin, int ksize);

@@ -481,8 +481,13 @@ constexpr int s16_min_waves(int MT, int EPI, int RPW, bool TP) {
 
 // The kernel body as a device function of (arguments, block index, blocks of this problem, batch element): k_conv_s16 runs one
 // problem per launch, k_conv_s16_pair two independent problems in ONE launch (block-index ranges), see below.
-template <int KS, int MT, int ROWS, int KSTEPS, int NSTAGE, int STRIDE, int EPI, int RS = 0, int RPW = 1, bool TP = false>
+// NPR = MFMA products per (k-step, tap): 3 = the fp16-split contraction (a_lo.b_hi + a_hi.b_lo + a_hi.b_hi, fp32-grade; k_conv_s16*),
+// 1 = a_hi.b_hi only (tcs_conv_s16_desc.products = 1; k_conv_s16_x1*): f16(x) . f16(w 2^s) with fp32 accumulation.  With one product a
+// stage stages only the hi plane of the activations and the hi pieces of the weights (half the DMA pieces and LDS), and a step
+// fetches one A and one B fragment.  The epilogues are the same code in both (the tap-partial fold stays a 3-product contraction).
+template <int KS, int MT, int ROWS, int KSTEPS, int NSTAGE, int STRIDE, int EPI, int RS = 0, int RPW = 1, bool TP = false, int NPR = 3>
 __device__ __forceinline__ void s16_conv_body(const S16Args& a, const int bid_, const int nblocks_, const int b) {
+    static_assert(NPR == 1 || NPR == 3, "products per k-step: 1 or 3");
     static_assert(!TP || (EPI == TCS_EPI_LINEAR && KS == 3 && STRIDE == 1), "tap partials: 3x3 stride-1 LINEAR launches");
     static_assert(!RS || (KS == 3 && STRIDE == 1), "row split is for 3x3 stride-1 convolutions");
     static_assert(ROWS % RPW == 0 && (RPW == 1 || (!RS && EPI != TCS_EPI_DECONV2X && EPI != TCS_EPI_BLEND9)), "rows per wave");
@@ -494,11 +499,12 @@ __device__ __forceinline__ void s16_conv_body(const S16Args& a, const int bid_, 
     constexpr bool GATHER = KS == 1 && STRIDE == 2;
     constexpr int LSTR = GATHER ? 1 : STRIDE;                                               // pixel stride inside the LDS tile
     constexpr int IH = RS ? ROWS : (GATHER ? ROWS : STRIDE * ROWS + KS - STRIDE), IW = GATHER ? 32 : STRIDE * 32 + KS - STRIDE, IN_CH = IH * IW;
-    constexpr int IN_UNITS = KSTEPS * 4 * IN_CH;                    // sub-tiles [kstep][lane half][hi|lo][IH][IW]
-    constexpr int NPI = (IN_UNITS + 63) / 64, NPW = KSTEPS * TS * MT * 2, NP = NPI + NPW;
+    constexpr int NPL = NPR == 3 ? 2 : 1;                           // planes staged: {hi, lo}, or hi only
+    constexpr int IN_UNITS = KSTEPS * 2 * NPL * IN_CH;              // sub-tiles [kstep][lane half][hi|lo][IH][IW] ([hi] with NPL = 1)
+    constexpr int NPI = (IN_UNITS + 63) / 64, NPW = KSTEPS * TS * MT * NPL, NP = NPI + NPW;
     constexpr int PPW = (NP + NW - 1) / NW;                         // DMA pieces per wave per stage
     constexpr int STAGE_BYTES = NP * 1024, W_OFF = NPI * 1024;
-    constexpr int NSTEP = KSTEPS * TS, R = 2 * RPW + 2 * MT;        // operand reads per (k-step, tap)
+    constexpr int NSTEP = KSTEPS * TS, R = NPL * (RPW + MT);        // operand reads per (k-step, tap)
     static_assert(R <= 15, "lgkmcnt field");
     static_assert(STAGE_BYTES <= 65536, "ds_read immediate offsets are 16 bits");
 
@@ -524,10 +530,12 @@ __device__ __forceinline__ void s16_conv_body(const S16Args& a, const int bid_, 
             // padded coordinates; RS adds the filter row (0..KS-1) through the stage's base pointer
             const int gy = GATHER ? min(STRIDE * (y0 + row) + 1, Hp - 1) : min(STRIDE * y0 + row - HALO + 1, Hp - 1 - (RS ? KS - 1 : 0));
             const int gx = GATHER ? min(STRIDE * (x0 + col) + 1, Wp - 1) : min(STRIDE * x0 + col - HALO + 1, Wp - 1);
-            voff[j] = ((unsigned)sub * plane + (unsigned)(gy * Wp + gx)) * 16u;
+            // sub = (kstep, half[, plane]); in HBM plane index (2 * group + {0: hi, 1: lo}), i.e. sub itself, or 2 * sub for hi only
+            voff[j] = ((unsigned)(NPL == 2 ? sub : 2 * sub) * plane + (unsigned)(gy * Wp + gx)) * 16u;
         } else {
             const int uw = (p - NPI) * 64 + lane;
-            const int slot = uw & 63, hl = (uw >> 6) & 1, m = (uw >> 7) % MT, kt = uw / (128 * MT);
+            const int q = uw >> (NPL == 2 ? 7 : 6);                  // (k-step x tap, cout tile) of this piece
+            const int slot = uw & 63, hl = NPL == 2 ? (uw >> 6) & 1 : 0, m = q % MT, kt = q / MT;
             const int gt = (kt / TS) * TAPS + kt % TS;              // global tap index relative to the stage's first one
             voff[j] = ((unsigned)(gt * a.nct32 + m) * 128u + hl * 64u + slot) * 16u;
         }
@@ -568,7 +576,7 @@ __device__ __forceinline__ void s16_conv_body(const S16Args& a, const int bid_, 
         for (int i = 0; i < 16; ++i) acc[m][i] = 0.f;
 
     // operand fetch addresses inside a stage buffer
-    const unsigned addr_b0 = lds_base + (unsigned)((half * 2 * IN_CH + LSTR * wave * RPW * IW + LSTR * l31) * 16);
+    const unsigned addr_b0 = lds_base + (unsigned)((half * NPL * IN_CH + LSTR * wave * RPW * IW + LSTR * l31) * 16);
     const unsigned addr_a0 = lds_base + (unsigned)(W_OFF + lane * 16);
     struct Frag { half8 b_hi[RPW], b_lo[RPW], a_hi[MT], a_lo[MT]; };
 #define S16_DSREAD(DST, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "i"(OFF) : "memory")
@@ -576,20 +584,22 @@ __device__ __forceinline__ void s16_conv_body(const S16Args& a, const int bid_, 
     {                                                                                                                 \
         const int kk_ = (STEP) / TS, t_ = (STEP) % TS, dy_ = RS ? 0 : t_ / KS, dx_ = t_ % KS;  /* constants after unrolling */ \
         _Pragma("unroll") for (int j = 0; j < RPW; ++j) {                                                             \
-            S16_DSREAD(F.b_hi[j], addr_b, ((kk_ * 4 + 0) * IN_CH + (dy_ + LSTR * j) * IW + dx_) * 16);                \
-            S16_DSREAD(F.b_lo[j], addr_b, ((kk_ * 4 + 1) * IN_CH + (dy_ + LSTR * j) * IW + dx_) * 16);                \
+            S16_DSREAD(F.b_hi[j], addr_b, ((kk_ * 2 * NPL + 0) * IN_CH + (dy_ + LSTR * j) * IW + dx_) * 16);          \
+            if constexpr (NPL == 2) S16_DSREAD(F.b_lo[j], addr_b, ((kk_ * 4 + 1) * IN_CH + (dy_ + LSTR * j) * IW + dx_) * 16); \
         }                                                                                                             \
         _Pragma("unroll") for (int m = 0; m < MT; ++m) {                                                              \
-            S16_DSREAD(F.a_hi[m], addr_a, (((kk_ * TS + t_) * MT + m) * 2 + 0) * 1024);                               \
-            S16_DSREAD(F.a_lo[m], addr_a, (((kk_ * TS + t_) * MT + m) * 2 + 1) * 1024);                               \
+            S16_DSREAD(F.a_hi[m], addr_a, (((kk_ * TS + t_) * MT + m) * NPL + 0) * 1024);                             \
+            if constexpr (NPL == 2) S16_DSREAD(F.a_lo[m], addr_a, (((kk_ * TS + t_) * MT + m) * 2 + 1) * 1024);       \
         }                                                                                                             \
     }
 #define S16_WAIT_LGKM(N) { asm volatile("s_waitcnt lgkmcnt(%0)" :: "i"(N) : "memory"); __builtin_amdgcn_sched_barrier(0); }
 #define S16_MMA(F)                                                                                                    \
     _Pragma("unroll") for (int m = 0; m < MT; ++m) {                                                                  \
         _Pragma("unroll") for (int j = 0; j < RPW; ++j) {                                                             \
-            acc[m * RPW + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.a_lo[m], F.b_hi[j], acc[m * RPW + j], 0, 0, 0); \
-            acc[m * RPW + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.a_hi[m], F.b_lo[j], acc[m * RPW + j], 0, 0, 0); \
+            if constexpr (NPR == 3) {                                                                                 \
+                acc[m * RPW + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.a_lo[m], F.b_hi[j], acc[m * RPW + j], 0, 0, 0); \
+                acc[m * RPW + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.a_hi[m], F.b_lo[j], acc[m * RPW + j], 0, 0, 0); \
+            }                                                                                                         \
             acc[m * RPW + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.a_hi[m], F.b_hi[j], acc[m * RPW + j], 0, 0, 0); \
         }                                                                                                             \
     }
@@ -675,6 +685,12 @@ __global__ __launch_bounds__(64 * ROWS / RPW, s16_min_waves(MT, EPI, RPW, TP)) v
     s16_conv_body<KS, MT, ROWS, KSTEPS, NSTAGE, STRIDE, EPI, RS, RPW, TP>(a, blockIdx.x, gridDim.x, blockIdx.y);
 }
 
+// the single-product body (tcs_conv_s16_desc.products = 1): same tiles, same occupancy targets, its own kernel name
+template <int KS, int MT, int ROWS, int KSTEPS, int NSTAGE, int STRIDE, int EPI, int RS = 0, int RPW = 1, bool TP = false>
+__global__ __launch_bounds__(64 * ROWS / RPW, s16_min_waves(MT, EPI, RPW, TP)) void k_conv_s16_x1(S16Args a) {
+    s16_conv_body<KS, MT, ROWS, KSTEPS, NSTAGE, STRIDE, EPI, RS, RPW, TP, 1>(a, blockIdx.x, gridDim.x, blockIdx.y);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Two independent convolutions as ONE launch ("grouped launch").  Inside a refinement iteration pairs of layers that do not
 // depend on each other (the two 3x3 layers of the motion encoder's halves, the second layers of the gradient predictor's
@@ -699,6 +715,22 @@ void k_conv_s16_pair(S16Args a0, S16Args a1, int n0, int n0pad) {
     } else {
         if ((int)threadIdx.x >= 64 * ROWS1) return;
         s16_conv_body<KS1, MT1, ROWS1, KST1, NST1, 1, EPI1>(a1, bid - n0pad, (int)gridDim.x - n0pad, blockIdx.y);
+    }
+}
+
+// the same with the single-product body on both sides (two descriptors pair only when their product counts match)
+template <int KS0, int MT0, int ROWS0, int KST0, int NST0, int EPI0, int KS1, int MT1, int ROWS1, int KST1, int NST1, int EPI1>
+__global__ __launch_bounds__(64 * (ROWS0 > ROWS1 ? ROWS0 : ROWS1),
+                             (s16_min_waves(MT0, EPI0, 1, false) < s16_min_waves(MT1, EPI1, 1, false) ? s16_min_waves(MT0, EPI0, 1, false)
+                                                                                                      : s16_min_waves(MT1, EPI1, 1, false)))
+void k_conv_s16_x1_pair(S16Args a0, S16Args a1, int n0, int n0pad) {
+    const int bid = blockIdx.x;
+    if (bid < n0pad) {
+        if (bid >= n0 || (int)threadIdx.x >= 64 * ROWS0) return;
+        s16_conv_body<KS0, MT0, ROWS0, KST0, NST0, 1, EPI0, 0, 1, false, 1>(a0, bid, n0, blockIdx.y);
+    } else {
+        if ((int)threadIdx.x >= 64 * ROWS1) return;
+        s16_conv_body<KS1, MT1, ROWS1, KST1, NST1, 1, EPI1, 0, 1, false, 1>(a1, bid - n0pad, (int)gridDim.x - n0pad, blockIdx.y);
     }
 }
 
@@ -759,6 +791,7 @@ __global__ __launch_bounds__(256) void k_s16_to_f32(const _Float16* __restrict__
 struct S16Plan {
     bool filled;
     long long key;                 // s16_key() of the instance
+    int nprod;                     // products per k-step of the instance (1 or 3): pairs form only between equal counts
     S16Args args;
     int nblocks, threads, B;
     size_t lds;
@@ -770,14 +803,16 @@ constexpr long long s16_key(int KS, int MT, int ROWS, int KSTEPS, int NSTAGE, in
     return ((((((((((long long)KS * 10 + MT) * 10 + ROWS) * 10 + KSTEPS) * 10 + NSTAGE) * 10 + STRIDE) * 10 + EPI) * 10 + RS) * 10 + RPW) * 2 + (TP ? 1 : 0));
 }
 
-template <int KS, int MT, int ROWS, int KSTEPS, int NSTAGE, int STRIDE, int EPI, int RS = 0, int RPW = 1, bool TP = false>
+template <int KS, int MT, int ROWS, int KSTEPS, int NSTAGE, int STRIDE, int EPI, int RS = 0, int RPW = 1, bool TP = false, int NPR = 3>
 static int launch_s16(S16Args& a, hipStream_t s) {
     constexpr bool GATHER = KS == 1 && STRIDE == 2;                 // (as in the kernel)
     constexpr int IH = RS ? ROWS : (GATHER ? ROWS : STRIDE * ROWS + KS - STRIDE), IW = GATHER ? 32 : STRIDE * 32 + KS - STRIDE, TS = RS ? KS : KS * KS;
-    constexpr int NPI = (KSTEPS * 4 * IH * IW + 63) / 64, NP = NPI + KSTEPS * TS * MT * 2;
+    constexpr int NPL = NPR == 3 ? 2 : 1;
+    constexpr int NPI = (KSTEPS * 2 * NPL * IH * IW + 63) / 64, NP = NPI + KSTEPS * TS * MT * NPL;
     constexpr size_t lds = (size_t)NSTAGE * NP * 1024;
     static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = k_conv_s16<KS, MT, ROWS, KSTEPS, NSTAGE, STRIDE, EPI, RS, RPW, TP>;
+    auto kern = NPR == 3 ? k_conv_s16<KS, MT, ROWS, KSTEPS, NSTAGE, STRIDE, EPI, RS, RPW, TP>
+                         : k_conv_s16_x1<KS, MT, ROWS, KSTEPS, NSTAGE, STRIDE, EPI, RS, RPW, TP>;
     a.npx = tcs_cdiv(a.W, 32);
     a.nct = a.nct32 / MT;
     a.npatch = a.npx * tcs_cdiv(a.H, ROWS);
@@ -786,9 +821,10 @@ static int launch_s16(S16Args& a, hipStream_t s) {
         S16Plan& p = *g_s16_plan;
         p.filled = true;
         p.key = s16_key(KS, MT, ROWS, KSTEPS, NSTAGE, STRIDE, EPI, RS, RPW, TP);
+        p.nprod = NPR;
         p.args = a;
         p.nblocks = a.npatch * a.nct; p.threads = 64 * ROWS / RPW; p.B = a.B; p.lds = lds;
-        p.launch_alone = &launch_s16<KS, MT, ROWS, KSTEPS, NSTAGE, STRIDE, EPI, RS, RPW, TP>;
+        p.launch_alone = &launch_s16<KS, MT, ROWS, KSTEPS, NSTAGE, STRIDE, EPI, RS, RPW, TP, NPR>;
         return TCS_OK;
     }
     (void)hipGetLastError();                                        // a stale error of an earlier runtime call is not ours
@@ -800,9 +836,10 @@ static int launch_s16(S16Args& a, hipStream_t s) {
     return tcs_launch_status();
 }
 
-template <int KS0, int MT0, int ROWS0, int KST0, int NST0, int EPI0, int KS1, int MT1, int ROWS1, int KST1, int NST1, int EPI1>
+template <int KS0, int MT0, int ROWS0, int KST0, int NST0, int EPI0, int KS1, int MT1, int ROWS1, int KST1, int NST1, int EPI1, int NPR>
 static int launch_s16_pair(const S16Plan& p0, const S16Plan& p1, hipStream_t s) {
-    auto kern = k_conv_s16_pair<KS0, MT0, ROWS0, KST0, NST0, EPI0, KS1, MT1, ROWS1, KST1, NST1, EPI1>;
+    auto kern = NPR == 3 ? k_conv_s16_pair<KS0, MT0, ROWS0, KST0, NST0, EPI0, KS1, MT1, ROWS1, KST1, NST1, EPI1>
+                         : k_conv_s16_x1_pair<KS0, MT0, ROWS0, KST0, NST0, EPI0, KS1, MT1, ROWS1, KST1, NST1, EPI1>;
     const size_t lds = p0.lds > p1.lds ? p0.lds : p1.lds;
     (void)hipGetLastError();
     if (lds > 64 * 1024) {
@@ -816,21 +853,21 @@ static int launch_s16_pair(const S16Plan& p0, const S16Plan& p1, hipStream_t s) 
 
 // tile configuration: cfg = CSPLIT*100000 + RS*10000 + MT*1000 + ROWS*100 + KSTEPS*10 + NSTAGE (0 = heuristic; CSPLIT: see
 // s16_block_tile; RS = 1: row split, RS = 2: two rows per wave); unknown combinations -> EUNSUPPORTED
-template <int KS, int STRIDE, int EPI>
+template <int KS, int STRIDE, int EPI, int NPR>
 static int launch_s16_cfg(S16Args& a, int cfg, hipStream_t s) {
 #define S16_CASE(MT_, ROWS_, KST_, NST_) \
-    case (MT_ * 1000 + ROWS_ * 100 + KST_ * 10 + NST_): return launch_s16<KS, MT_, ROWS_, KST_, NST_, STRIDE, EPI>(a, s);
+    case (MT_ * 1000 + ROWS_ * 100 + KST_ * 10 + NST_): return launch_s16<KS, MT_, ROWS_, KST_, NST_, STRIDE, EPI, 0, 1, false, NPR>(a, s);
 #define S16_CASE_RS(MT_, ROWS_, KST_, NST_) \
-    case (10000 + MT_ * 1000 + ROWS_ * 100 + KST_ * 10 + NST_): return launch_s16<KS, MT_, ROWS_, KST_, NST_, STRIDE, EPI, 1>(a, s);
+    case (10000 + MT_ * 1000 + ROWS_ * 100 + KST_ * 10 + NST_): return launch_s16<KS, MT_, ROWS_, KST_, NST_, STRIDE, EPI, 1, 1, false, NPR>(a, s);
 #define S16_CASE_RPW2(MT_, ROWS_, KST_, NST_) \
-    case (20000 + MT_ * 1000 + ROWS_ * 100 + KST_ * 10 + NST_): return launch_s16<KS, MT_, ROWS_, KST_, NST_, STRIDE, EPI, 0, 2>(a, s);
+    case (20000 + MT_ * 1000 + ROWS_ * 100 + KST_ * 10 + NST_): return launch_s16<KS, MT_, ROWS_, KST_, NST_, STRIDE, EPI, 0, 2, false, NPR>(a, s);
     if constexpr (KS == 3 && STRIDE == 1 && EPI == TCS_EPI_LINEAR) {
         if (a.tap_out) {                                // tap partials: their own instances (see s16_epilogue_tile), the tiles the loop uses
             switch (cfg) {
-                case 1411: return launch_s16<KS, 1, 4, 1, 1, STRIDE, EPI, 0, 1, true>(a, s);
-                case 1412: return launch_s16<KS, 1, 4, 1, 2, STRIDE, EPI, 0, 1, true>(a, s);
-                case 1812: return launch_s16<KS, 1, 8, 1, 2, STRIDE, EPI, 0, 1, true>(a, s);
-                case 21812: return launch_s16<KS, 1, 8, 1, 2, STRIDE, EPI, 0, 2, true>(a, s);
+                case 1411: return launch_s16<KS, 1, 4, 1, 1, STRIDE, EPI, 0, 1, true, NPR>(a, s);
+                case 1412: return launch_s16<KS, 1, 4, 1, 2, STRIDE, EPI, 0, 1, true, NPR>(a, s);
+                case 1812: return launch_s16<KS, 1, 8, 1, 2, STRIDE, EPI, 0, 1, true, NPR>(a, s);
+                case 21812: return launch_s16<KS, 1, 8, 1, 2, STRIDE, EPI, 0, 2, true, NPR>(a, s);
                 default: return TCS_EUNSUPPORTED;
             }
         }
@@ -910,6 +947,46 @@ static int s16_heuristic(const S16Args& a, int ksize, int stride, int kst1x1, in
     return 100000 + 1000 + 400 + 10 + 2;
 }
 
+// the epilogue's checks and the launch, for the product count of the descriptor
+template <int NPR>
+static int s16_launch_epi(const tcs_conv_s16_desc* d, S16Args& a, int cfg, int stride, hipStream_t s) {
+    switch (d->epilogue) {
+        case TCS_EPI_LINEAR:
+            if (stride == 2 && d->ksize == 1) return launch_s16_cfg<1, 2, TCS_EPI_LINEAR, NPR>(a, cfg, s);
+            if (stride == 2) return launch_s16_cfg<3, 2, TCS_EPI_LINEAR, NPR>(a, cfg, s);
+            return d->ksize == 3 ? launch_s16_cfg<3, 1, TCS_EPI_LINEAR, NPR>(a, cfg, s) : launch_s16_cfg<1, 1, TCS_EPI_LINEAR, NPR>(a, cfg, s);
+        case TCS_EPI_BLEND9:
+            if (d->ksize != 1 || stride != 1 || d->Cout != 9 || !d->blend_cand || d->blend_cand_ctot < 9 || !d->blend_refined) return TCS_EINVAL;
+            if (d->blend_delta && !d->blend_disp) return TCS_EINVAL;
+            if (d->blend_flow16 && (d->blend_flow16_channel < 0 || d->blend_flow16_channel >= 8 * d->blend_flow16_groups)) return TCS_EINVAL;
+            a.bl_cand = d->blend_cand; a.bl_cand_ctot = d->blend_cand_ctot; a.bl_disp = d->blend_disp;
+            a.bl_refined = d->blend_refined; a.bl_delta = d->blend_delta; a.bl_coords1 = d->blend_coords1; a.bl_flow = d->blend_flow_x;
+            a.bl_f16 = reinterpret_cast<_Float16*>(d->blend_flow16); a.bl_f16_groups = d->blend_flow16_groups; a.bl_f16_ch = d->blend_flow16_channel;
+            if (d->blend_warm_pyr[0]) {
+                if (!d->blend_warm_pyr[1] || !d->blend_warm_pyr[2] || !d->blend_warm_pyr[3] || d->blend_warm_radius < 0 || d->blend_warm_radius > 16 ||
+                    d->W < 8) return TCS_EINVAL;
+                a.warm_pyr0 = d->blend_warm_pyr[0]; a.warm_pyr1 = d->blend_warm_pyr[1]; a.warm_pyr2 = d->blend_warm_pyr[2];
+                a.warm_pyr3 = d->blend_warm_pyr[3]; a.warm_radius = d->blend_warm_radius;
+            }
+            return launch_s16_cfg<1, 1, TCS_EPI_BLEND9, NPR>(a, cfg, s);
+        case TCS_EPI_DECONV2X:
+            if (d->ksize != 3 || !a.out16 || d->Cout % 32 != 0) return TCS_EINVAL;
+            a.hidden = d->Cout / 4;
+            return launch_s16_cfg<3, 1, TCS_EPI_DECONV2X, NPR>(a, cfg, s);
+        case TCS_EPI_GRU_ZR:
+            if (!a.h || !a.out16 || !a.out32 || d->Cout % 64 != 0) return TCS_EINVAL;
+            a.hidden = d->Cout / 2;
+            if (a.h_groups < a.hidden / 8) return TCS_EINVAL;
+            return d->ksize == 3 ? launch_s16_cfg<3, 1, TCS_EPI_GRU_ZR, NPR>(a, cfg, s) : launch_s16_cfg<1, 1, TCS_EPI_GRU_ZR, NPR>(a, cfg, s);
+        case TCS_EPI_GRU_Q:
+            if (!a.h || !a.z || !a.out16 || d->Cout % 32 != 0) return TCS_EINVAL;
+            a.hidden = d->Cout;
+            if (a.h_groups < a.hidden / 8) return TCS_EINVAL;
+            return d->ksize == 3 ? launch_s16_cfg<3, 1, TCS_EPI_GRU_Q, NPR>(a, cfg, s) : launch_s16_cfg<1, 1, TCS_EPI_GRU_Q, NPR>(a, cfg, s);
+        default: return TCS_EINVAL;
+    }
+}
+
 extern "C" {
 
 size_t tcs_deconv_in_stats_bytes(int B, int C, int H, int W) {
@@ -947,6 +1024,8 @@ int tcs_conv2d_s16(const tcs_conv_s16_desc* d, tcs_stream_t stream) {
     if (!d || !d->weight || d->n_src < 1 || d->n_src > TCS_MAX_SRC) return TCS_EINVAL;
     if (d->B <= 0 || d->B > 65535 || d->H <= 0 || d->W <= 0 || d->Cout <= 0) return TCS_EINVAL;
     if (d->ksize != 1 && d->ksize != 3) return TCS_EUNSUPPORTED;
+    const int nprod = d->products == 0 ? 3 : d->products;          // 0 (zero-filled descriptor) = the fp16-split contraction
+    if (nprod != 1 && nprod != 3) return TCS_EINVAL;
     const int stride = d->stride == 2 ? 2 : 1;
     if (stride == 2 && d->epilogue != TCS_EPI_LINEAR) return TCS_EUNSUPPORTED;
     S16Args a;
@@ -1038,59 +1117,35 @@ int tcs_conv2d_s16(const tcs_conv_s16_desc* d, tcs_stream_t stream) {
         if (d->addend_ctot != 0 && d->addend_ctot < own) return TCS_EINVAL;
         a.add_ctot = d->addend_ctot ? d->addend_ctot : own;
     }
-    switch (d->epilogue) {
-        case TCS_EPI_LINEAR:
-            if (stride == 2 && d->ksize == 1) return launch_s16_cfg<1, 2, TCS_EPI_LINEAR>(a, cfg, s);
-            if (stride == 2) return launch_s16_cfg<3, 2, TCS_EPI_LINEAR>(a, cfg, s);
-            return d->ksize == 3 ? launch_s16_cfg<3, 1, TCS_EPI_LINEAR>(a, cfg, s) : launch_s16_cfg<1, 1, TCS_EPI_LINEAR>(a, cfg, s);
-        case TCS_EPI_BLEND9:
-            if (d->ksize != 1 || stride != 1 || d->Cout != 9 || !d->blend_cand || d->blend_cand_ctot < 9 || !d->blend_refined) return TCS_EINVAL;
-            if (d->blend_delta && !d->blend_disp) return TCS_EINVAL;
-            if (d->blend_flow16 && (d->blend_flow16_channel < 0 || d->blend_flow16_channel >= 8 * d->blend_flow16_groups)) return TCS_EINVAL;
-            a.bl_cand = d->blend_cand; a.bl_cand_ctot = d->blend_cand_ctot; a.bl_disp = d->blend_disp;
-            a.bl_refined = d->blend_refined; a.bl_delta = d->blend_delta; a.bl_coords1 = d->blend_coords1; a.bl_flow = d->blend_flow_x;
-            a.bl_f16 = reinterpret_cast<_Float16*>(d->blend_flow16); a.bl_f16_groups = d->blend_flow16_groups; a.bl_f16_ch = d->blend_flow16_channel;
-            if (d->blend_warm_pyr[0]) {
-                if (!d->blend_warm_pyr[1] || !d->blend_warm_pyr[2] || !d->blend_warm_pyr[3] || d->blend_warm_radius < 0 || d->blend_warm_radius > 16 ||
-                    d->W < 8) return TCS_EINVAL;
-                a.warm_pyr0 = d->blend_warm_pyr[0]; a.warm_pyr1 = d->blend_warm_pyr[1]; a.warm_pyr2 = d->blend_warm_pyr[2];
-                a.warm_pyr3 = d->blend_warm_pyr[3]; a.warm_radius = d->blend_warm_radius;
-            }
-            return launch_s16_cfg<1, 1, TCS_EPI_BLEND9>(a, cfg, s);
-        case TCS_EPI_DECONV2X:
-            if (d->ksize != 3 || !a.out16 || d->Cout % 32 != 0) return TCS_EINVAL;
-            a.hidden = d->Cout / 4;
-            return launch_s16_cfg<3, 1, TCS_EPI_DECONV2X>(a, cfg, s);
-        case TCS_EPI_GRU_ZR:
-            if (!a.h || !a.out16 || !a.out32 || d->Cout % 64 != 0) return TCS_EINVAL;
-            a.hidden = d->Cout / 2;
-            if (a.h_groups < a.hidden / 8) return TCS_EINVAL;
-            return d->ksize == 3 ? launch_s16_cfg<3, 1, TCS_EPI_GRU_ZR>(a, cfg, s) : launch_s16_cfg<1, 1, TCS_EPI_GRU_ZR>(a, cfg, s);
-        case TCS_EPI_GRU_Q:
-            if (!a.h || !a.z || !a.out16 || d->Cout % 32 != 0) return TCS_EINVAL;
-            a.hidden = d->Cout;
-            if (a.h_groups < a.hidden / 8) return TCS_EINVAL;
-            return d->ksize == 3 ? launch_s16_cfg<3, 1, TCS_EPI_GRU_Q>(a, cfg, s) : launch_s16_cfg<1, 1, TCS_EPI_GRU_Q>(a, cfg, s);
-        default: return TCS_EINVAL;
-    }
+    return nprod == 1 ? s16_launch_epi<1>(d, a, cfg, stride, s) : s16_launch_epi<3>(d, a, cfg, stride, s);
 }
 
 // Pair kernels exist for the instance combinations the refinement loop groups (core/update.py); any other combination, and
 // anything the planner cannot take (ablation builds), runs as two ordinary launches: the results are the same either way.
-static int s16_launch_pair(const S16Plan& p0, const S16Plan& p1, hipStream_t s) {
+}  // extern "C"
+
+template <int NPR>
+static int s16_launch_pair_n(const S16Plan& p0, const S16Plan& p1, hipStream_t s) {
     constexpr int L = TCS_EPI_LINEAR;
     constexpr long long k3412 = s16_key(3, 1, 4, 1, 2, 1, L, 0, 1, false), k3812 = s16_key(3, 1, 8, 1, 2, 1, L, 0, 1, false),
                         k1422 = s16_key(1, 1, 4, 2, 2, 1, L, 0, 1, false), k3411 = s16_key(3, 1, 4, 1, 1, 1, L, 0, 1, false);
     if (p0.B == p1.B) {
-        if (p0.key == k3412 && p1.key == k3412) return launch_s16_pair<3, 1, 4, 1, 2, L, 3, 1, 4, 1, 2, L>(p0, p1, s);
+        if (p0.key == k3412 && p1.key == k3412) return launch_s16_pair<3, 1, 4, 1, 2, L, 3, 1, 4, 1, 2, L, NPR>(p0, p1, s);
         // 4-row single-stage 3x3 tile (31 KiB) beside the 1x1 tile (40 KiB): every workgroup of the launch is allocated the LARGER of
         // the two LDS sizes, and with the 8-row two-stage 3x3 tile (80 KiB) the 1x1 half ran two workgroups per CU instead of four
-        if (p0.key == k3411 && p1.key == k1422) return launch_s16_pair<3, 1, 4, 1, 1, L, 1, 1, 4, 2, 2, L>(p0, p1, s);
-        if (p0.key == k1422 && p1.key == k3411) return launch_s16_pair<3, 1, 4, 1, 1, L, 1, 1, 4, 2, 2, L>(p1, p0, s);
-        if (p0.key == k3812 && p1.key == k1422) return launch_s16_pair<3, 1, 8, 1, 2, L, 1, 1, 4, 2, 2, L>(p0, p1, s);
-        if (p0.key == k1422 && p1.key == k3812) return launch_s16_pair<3, 1, 8, 1, 2, L, 1, 1, 4, 2, 2, L>(p1, p0, s);
+        if (p0.key == k3411 && p1.key == k1422) return launch_s16_pair<3, 1, 4, 1, 1, L, 1, 1, 4, 2, 2, L, NPR>(p0, p1, s);
+        if (p0.key == k1422 && p1.key == k3411) return launch_s16_pair<3, 1, 4, 1, 1, L, 1, 1, 4, 2, 2, L, NPR>(p1, p0, s);
+        if (p0.key == k3812 && p1.key == k1422) return launch_s16_pair<3, 1, 8, 1, 2, L, 1, 1, 4, 2, 2, L, NPR>(p0, p1, s);
+        if (p0.key == k1422 && p1.key == k3812) return launch_s16_pair<3, 1, 8, 1, 2, L, 1, 1, 4, 2, 2, L, NPR>(p1, p0, s);
     }
     return 1;           // no pair kernel
+}
+
+extern "C" {
+
+static int s16_launch_pair(const S16Plan& p0, const S16Plan& p1, hipStream_t s) {
+    if (p0.nprod != p1.nprod) return 1;             // a 1-product and a 3-product layer: two launches
+    return p0.nprod == 1 ? s16_launch_pair_n<1>(p0, p1, s) : s16_launch_pair_n<3>(p0, p1, s);
 }
 
 int tcs_conv2d_s16_group(const tcs_conv_s16_desc* const* descs, int n, tcs_stream_t stream) {
@@ -1129,7 +1184,7 @@ int tcs_conv2d_s16_group_fused(const tcs_conv_s16_desc* const* descs, int n) {
     constexpr int L = TCS_EPI_LINEAR;
     const long long k3412 = s16_key(3, 1, 4, 1, 2, 1, L, 0, 1, false), k3812 = s16_key(3, 1, 8, 1, 2, 1, L, 0, 1, false),
                     k1422 = s16_key(1, 1, 4, 2, 2, 1, L, 0, 1, false), k3411 = s16_key(3, 1, 4, 1, 1, 1, L, 0, 1, false);
-    if (plan[0].B != plan[1].B) return 0;
+    if (plan[0].B != plan[1].B || plan[0].nprod != plan[1].nprod) return 0;
     const long long a = plan[0].key, b = plan[1].key;
     return (a == k3412 && b == k3412) || (a == k3812 && b == k1422) || (a == k1422 && b == k3812) || (a == k3411 && b == k1422) ||
            (a == k1422 && b == k3411);

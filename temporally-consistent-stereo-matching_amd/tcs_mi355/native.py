@@ -37,6 +37,7 @@ class ConvDesc(C.Structure):
         ("stride", c_int), ("math", c_int), ("weight_unscale", c_f),
         ("out16", c_fp), ("out16_groups", c_int), ("out16_group_offset", c_int),
         ("in_transform", c_int), ("src_batch2", c_fp), ("batch_split", c_int),
+        ("products", c_int),
     ]
 
 
@@ -59,6 +60,7 @@ class ConvS16Desc(C.Structure):
         ("in_stats", c_fp), ("in_eps", c_f),
         ("tap_weights", c_fp), ("tap_out", c_fp), ("tap_nout", c_int), ("tap_tiles", c_int), ("tap_unscale", c_f),
         ("blend_warm_pyr", c_fp * 4), ("blend_warm_radius", c_int),
+        ("products", c_int),
     ]
 
 

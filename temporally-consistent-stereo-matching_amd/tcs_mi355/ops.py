@@ -315,11 +315,15 @@ class PackedConv:
     ksize: int
     math: int = MATH_F32
     unscale: float = 1.0
+    products: int = 0              # MATH_F16X3: MFMA products per k-step (tcs_conv*_desc.products): 0 / 3 = fp16-split, 1 = fp16 only
 
 
-def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor], math: str = "f32") -> PackedConv:
+def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor], math: str = "f32", products: int = 0) -> PackedConv:
     """math='f32': fp32 MFMA kernel.  math='f16x3': fp16 hi/lo split kernel (fp32-equivalent accuracy);
-    falls back to 'f32' for the shapes the split kernel does not cover (Cin == 1, 7x7)."""
+    falls back to 'f32' for the shapes the split kernel does not cover (Cin == 1, 7x7).  `products` = 1: the f16x3 packing is
+    contracted on its hi halves only (f16(x) * f16(w), fp32 accumulation; tcs_conv_desc.products); ignored by the 'f32' layout."""
+    if products not in (0, 1, 3):
+        raise ValueError(f"products must be 0, 1 or 3, got {products!r}")
     cout, cin, kh, kw = (int(s) for s in weight.shape)
     if kh != kw:
         raise ValueError("square kernels only")
@@ -334,7 +338,7 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor], math: str = "f
         packed = torch.empty(n, dtype=torch.float32, device=w.device)
         nv.check(L.tcs_pack_conv_weight_f16x3(nv.ptr(w, "weight"), cout, cin, kh, s_log2, nv.ptr(packed), nv.stream()),
                  "tcs_pack_conv_weight_f16x3")
-        return PackedConv(packed, b, cout, cin, kh, MATH_F16X3, 2.0 ** (-s_log2))
+        return PackedConv(packed, b, cout, cin, kh, MATH_F16X3, 2.0 ** (-s_log2), int(products))
     if math not in ("f32", "f16x3"):
         raise ValueError(f"unknown math mode {math!r}")
     n = L.tcs_conv_packed_floats(cout, cin, kh)
@@ -345,9 +349,11 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor], math: str = "f
     return PackedConv(packed, b, cout, cin, kh)
 
 
-def pack_deconv4x4s2(weight: torch.Tensor) -> PackedConv:
+def pack_deconv4x4s2(weight: torch.Tensor, products: int = 0) -> PackedConv:
     """nn.ConvTranspose2d(Cin, Cout, 4, stride=2, padding=1, bias=False) -> the fp16-split layout of the equivalent
-    3x3 convolution with 4*Cout parity-grouped outputs (tcs_pack_deconv4x4s2_f16x3); use with `deconv4x4s2`."""
+    3x3 convolution with 4*Cout parity-grouped outputs (tcs_pack_deconv4x4s2_f16x3); use with `deconv4x4s2`.  `products`: as pack_conv."""
+    if products not in (0, 1, 3):
+        raise ValueError(f"products must be 0, 1 or 3, got {products!r}")
     cin, cout, kh, kw = (int(s) for s in weight.shape)
     if (kh, kw) != (4, 4):
         raise ValueError("4x4 transposed convolutions only")
@@ -359,7 +365,7 @@ def pack_deconv4x4s2(weight: torch.Tensor) -> PackedConv:
     scratch = torch.empty(4 * cout * cin * 9, dtype=torch.float32, device=w.device)
     nv.check(L.tcs_pack_deconv4x4s2_f16x3(nv.ptr(w, "weight"), cin, cout, s_log2, nv.ptr(packed), nv.ptr(scratch), nv.stream()),
              "tcs_pack_deconv4x4s2_f16x3")
-    return PackedConv(packed, None, 4 * cout, cin, 3, MATH_F16X3, 2.0 ** (-s_log2))
+    return PackedConv(packed, None, 4 * cout, cin, 3, MATH_F16X3, 2.0 ** (-s_log2), int(products))
 
 
 def deconv4x4s2(pc: PackedConv, srcs: Sequence[torch.Tensor], out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -412,6 +418,7 @@ def _desc(pc: PackedConv, srcs: Sequence[torch.Tensor]) -> nv.ConvDesc:
     d.B, d.H, d.W, d.Cin, d.Cout, d.ksize = B, H, W, pc.cin, pc.cout, pc.ksize
     d.post_scale = 1.0
     d.math, d.weight_unscale = pc.math, pc.unscale
+    d.products = pc.products if pc.math == MATH_F16X3 else 0
     return d
 
 

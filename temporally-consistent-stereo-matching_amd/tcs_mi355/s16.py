@@ -119,8 +119,11 @@ class S16Pool:
     buffer for the same key and shape.  Producers write interior pixels of real channel groups only, so borders and
     padding channels stay zero without any per-frame memset."""
 
-    def __init__(self):
+    def __init__(self, products: int = 0):
         self.buffers: Dict[tuple, S16] = {}
+        # MFMA products per k-step of the fp16-split convolutions of the model that owns the pool (tcs_conv*_desc.products): 0 = the
+        # fp16-split contraction, 1 = fp16 operands (TCStereo's hip_precision="fp16").  Fixed for the pool's life.
+        self.products = int(products)
 
     def get(self, key, B, C_, H, W, device, groups=None) -> S16:
         G = groups_for(C_) if groups is None else int(groups)
@@ -193,6 +196,7 @@ def _desc(pc: PackedConv, srcs: Sequence[S16], stride: int = 1) -> nv.ConvS16Des
     d.weight, d.bias = nv.ptr(pc.weight), nv.ptr(pc.bias)
     d.B, d.H, d.W, d.Cin, d.Cout, d.ksize, d.stride = B, H, W, pc.cin, pc.cout, pc.ksize, stride
     d.post_scale, d.weight_unscale = 1.0, pc.unscale
+    d.products = pc.products
     return d
 
 
