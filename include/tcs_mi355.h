@@ -36,7 +36,7 @@ extern "C" {
 typedef void* tcs_stream_t;
 
 int tcs_abi_version(void);                 /* bumped when a signature changes (7: grouped launches, blend_warm_*; 8: `products`, the
-                                              last field of tcs_conv_desc and tcs_conv_s16_desc) */
+                                              last field of tcs_conv_desc and tcs_conv_s16_desc; 9: the ordered splat entry points) */
 const char* tcs_error_string(int code);
 
 /* ------------------------------------------------------------------------------------------------
@@ -101,13 +101,38 @@ size_t tcs_warp_workspace_bytes(int B, int C, int H, int W);
  *   out_fmap [B,C,H,W]                                                       (nullable)
  *   cur_fmap [B,C,H,W] + out_cost [B,1,H,W]: cosine cost vs the current frame (both or none)
  * Float atomics are used for the splat, like the reference's atomicAdd: the summation order, and
- * therefore the last bits, can differ from run to run.
+ * therefore the last bits, can differ from run to run (tcs_warp_forward_ordered below fixes the order).
  */
 int tcs_warp_forward(const float* prev_disp, const float* prev_fmap, const float* T_rel, const float* K,
                      const float* K_inv, const float* baseline, int B, int C, int H, int W,
                      float* out_disp, float* out_fmap, float* out_mask,
                      const float* cur_fmap, float* out_cost,
                      void* workspace, tcs_stream_t stream);
+
+/*
+ * Ordered splat (tcs_warp_forward_ordered, tcs_softsplat_sum_ordered): bit-reproducible from run to run, whatever the scheduling,
+ * the stream, graph or eager launches, or what runs beside it.  The contributions are those of the atomic splat; their sum has a
+ * fixed order.  For source pixel p = y*W + x of batch element b (batch elements are independent):
+ *   fx = (float)x + flow[b,0,p], fy = (float)y + flow[b,1,p]; no contribution if fx or fy is not finite, if valid[b,p] == 0
+ *   (warp only), or unless -2 <= floor(fx) <= W and -2 <= floor(fy) <= H.  x0 = floor(fx), y0 = floor(fy); corner weights
+ *   w00 = (x0+1-fx)*(y0+1-fy), w10 = (fx-x0)*(y0+1-fy), w01 = (x0+1-fx)*(fy-y0), w11 = (fx-x0)*(fy-y0) (each op one fp32 rounding),
+ *   each to target (x0+dx, y0+dy) when that is inside the frame.
+ * Target t's channel c is    acc = 0;  for its contributions in ASCENDING p:  acc = fl(acc + fl(v * w))
+ * in plain fp32 (no FMA contraction), v = in[b,c,p] (summation splat) or, for warp(), fl(v' * s) with s = expf(clamp(cur_disp[p] -
+ * mean, +-50)) and v' = prev_fmap[b,c,p] (channels < C), cur_disp[p] (the disparity sum) or 1 (the normaliser, v = s).  A source adds
+ * at most one corner to a target, so the order is total.  warp() then normalises, splits and forms the cosine cost exactly as
+ * tcs_warp_forward does.  Same arguments and outputs as the atomic entry points, except that tcs_softsplat_sum_ordered WRITES `out`
+ * (no zeroing needed) and both take a workspace of their own size query.  Needs B*4*H*W < 2^31.
+ */
+size_t tcs_warp_ordered_workspace_bytes(int B, int C, int H, int W);
+int tcs_warp_forward_ordered(const float* prev_disp, const float* prev_fmap, const float* T_rel, const float* K,
+                             const float* K_inv, const float* baseline, int B, int C, int H, int W,
+                             float* out_disp, float* out_fmap, float* out_mask,
+                             const float* cur_fmap, float* out_cost,
+                             void* workspace, tcs_stream_t stream);
+size_t tcs_softsplat_ordered_workspace_bytes(int B, int H, int W);
+int tcs_softsplat_sum_ordered(const float* in, const float* flow, int B, int C, int H, int W, float* out, void* workspace,
+                              tcs_stream_t stream);
 
 /* The pre-splat quantities of warp() (geo_utils.py:169-193), exposed for parity tests:
  * cur_disp, valid, flow [B,2,H,W], metric — all [B,1,H,W] unless noted. */

@@ -53,6 +53,10 @@ class TCStereo(nn.Module):
         if precision not in HIP_PRECISIONS:
             raise ValueError(f"hip_precision must be one of {sorted(HIP_PRECISIONS)}, got {precision!r}")
         self._hip_precision = precision
+        deterministic = getattr(args, "hip_deterministic", False)
+        if not isinstance(deterministic, bool):
+            raise ValueError(f"hip_deterministic must be a bool, got {deterministic!r}")
+        self._hip_deterministic = deterministic
         self.args = args
         self.scale_rate = 1 / (2 ** args.n_downsample)
         hd = list(args.hidden_dims)
@@ -86,6 +90,12 @@ class TCStereo(nn.Module):
     def hip_precision(self) -> str:
         """"fp32" or "fp16": the arithmetic of this model's fp16-split convolutions, fixed at construction (args.hip_precision)."""
         return self._hip_precision
+
+    @property
+    def hip_deterministic(self) -> bool:
+        """True: the temporal warp's splat sums in a fixed order (ops.warp_forward(ordered=True)), so that every frame of a sequence is
+        bit-reproducible from run to run; fixed at construction (args.hip_deterministic, default False: the float-atomic splat)."""
+        return self._hip_deterministic
 
     def freeze_bn(self):
         for m in self.modules():
@@ -240,7 +250,7 @@ class TCStereo(nn.Module):
             # warp + normalise + cosine cost in one launch sequence; the warped feature map is never materialised
             sparse_disp, _, sparse_mask, cost = ops.warp_forward(
                 (-last_disp).float().contiguous(), last_fmap1.float().contiguous(), relative_T, K_scale,
-                K_scale_inv, baseline, cur_fmap=fmap1, want_fmap=False)
+                K_scale_inv, baseline, cur_fmap=fmap1, want_fmap=False, ordered=self._hip_deterministic)
 
         pool = self._s16pool
         s16_head = "dc32" not in _X

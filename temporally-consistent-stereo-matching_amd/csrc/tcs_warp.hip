@@ -8,6 +8,7 @@
 // atomic wave-instruction covers ~256 contiguous bytes of one NCHW channel plane — the shape the
 // memory-side f32 atomics of MI355X run fastest on.  Geometry (flow, weights, exp(metric)) is
 // computed once per thread, not once per (channel, pixel) as the reference kernel does.
+// The opt-in ordered splat (k_ord_*, below) sums the same contributions per target in ascending source order: bit-reproducible.
 #include "tcs_common.h"
 
 struct Cam {
@@ -188,6 +189,223 @@ __global__ __launch_bounds__(256) void k_warp_finish(const float* __restrict__ a
 }
 
 // ------------------------------------------------------------------------------------------------
+// Ordered splat (tcs_warp_forward_ordered, tcs_softsplat_sum_ordered): the same contributions as k_splat, summed per target in
+// ascending source-pixel order with plain fp32 adds, so the result does not depend on scheduling.  Inverted index per batch element:
+//   count  (integer atomics: contributions per target)  ->  scan (exclusive prefix sum: bucket offsets)  ->  place (each in-frame
+//   corner once into its target's bucket, atomic cursor)  ->  rank (each entry moves to start + #entries of its bucket with a smaller
+//   source index: the bucket is now sorted; sources are distinct within a bucket)  ->  gather (one lane per target sums its bucket).
+// Bucket entries carry the corner weight computed exactly as k_splat computes it.  A bucket is summed by one lane (per channel
+// quarter), so its time is linear in its length: real motion puts 1-4 entries in a bucket; a degenerate pose or flow that sends
+// every source to one target is correct but serialised on that lane.
+// ------------------------------------------------------------------------------------------------
+// k_splat's skip rules for source pixel p of batch element b: returns the mask of in-frame corners (bit k: 0 = (x0,y0),
+// 1 = (x0+1,y0), 2 = (x0,y0+1), 3 = (x0+1,y0+1)), the target of corner 0 and the four corner weights.
+template <int MODE>
+__device__ __forceinline__ int ord_corners(const float* __restrict__ flow, const float* __restrict__ valid, int b, int p, int H, int W,
+                                           int& tnw, float w[4]) {
+#pragma clang fp contract(off)
+    const int HW = H * W, y = p / W, x = p - y * W;
+    const float fx = (float)x + flow[((size_t)b * 2 + 0) * HW + p];
+    const float fy = (float)y + flow[((size_t)b * 2 + 1) * HW + p];
+    if (!isfinite(fx) || !isfinite(fy)) return 0;
+    if (MODE == 1 && valid[(size_t)b * HW + p] == 0.f) return 0;
+    const float x0f = floorf(fx), y0f = floorf(fy);
+    if (!(x0f >= -2.f && x0f <= (float)W && y0f >= -2.f && y0f <= (float)H)) return 0;
+    const int x0 = (int)x0f, y0 = (int)y0f;
+    w[0] = ((float)(x0 + 1) - fx) * ((float)(y0 + 1) - fy);
+    w[1] = (fx - (float)x0) * ((float)(y0 + 1) - fy);
+    w[2] = ((float)(x0 + 1) - fx) * (fy - (float)y0);
+    w[3] = (fx - (float)x0) * (fy - (float)y0);
+    const bool xl = x0 >= 0 && x0 < W, xr = x0 + 1 >= 0 && x0 + 1 < W;
+    const bool yt = y0 >= 0 && y0 < H, yb = y0 + 1 >= 0 && y0 + 1 < H;
+    tnw = y0 * W + x0;
+    return (xl && yt ? 1 : 0) | (xr && yt ? 2 : 0) | (xl && yb ? 4 : 0) | (xr && yb ? 8 : 0);
+}
+
+__device__ __forceinline__ int ord_target(int tnw, int k, int W) { return tnw + (k & 1) + (k >> 1) * W; }
+
+// count[b*HW + t] += contributions to target t; MODE 1 also stores the source's exp(metric) scale (as k_splat computes it)
+template <int MODE>
+__global__ __launch_bounds__(256) void k_ord_count(const float* __restrict__ flow, const float* __restrict__ cur_disp,
+                                                   const float* __restrict__ valid, const float* __restrict__ mean, int H, int W,
+                                                   int* __restrict__ count, float* __restrict__ scale) {
+    const int b = blockIdx.y, HW = H * W;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= HW) return;
+    int tnw;
+    float w[4];
+    const int m = ord_corners<MODE>(flow, valid, b, p, H, W, tnw, w);
+    if (!m) return;
+    if (MODE == 1) scale[(size_t)b * HW + p] = expf(fminf(fmaxf(cur_disp[(size_t)b * HW + p] - *mean, -50.f), 50.f));
+    int* cb = count + (size_t)b * HW;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (m & (1 << k)) atomicAdd(cb + ord_target(tnw, k, W), 1);
+}
+
+// exclusive prefix sum of one batch element's counts (one block per element): start = cursor = b*4*HW + offset, total[b] = entries
+__global__ __launch_bounds__(1024) void k_ord_scan(const int* __restrict__ count, int HW, int* __restrict__ start, int* __restrict__ cursor,
+                                                   int* __restrict__ total) {
+    __shared__ int s[1024];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int per = (HW + 1023) / 1024, lo = min(HW, t * per), hi = min(HW, lo + per);
+    const int* c = count + (size_t)b * HW;
+    int sum = 0;
+    for (int i = lo; i < hi; ++i) sum += c[i];
+    s[t] = sum;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+        const int v = t >= off ? s[t - off] : 0;
+        __syncthreads();
+        s[t] += v;
+        __syncthreads();
+    }
+    int run = b * 4 * HW + s[t] - sum;
+    for (int i = lo; i < hi; ++i) {
+        start[(size_t)b * HW + i] = run;
+        cursor[(size_t)b * HW + i] = run;
+        run += c[i];
+    }
+    if (t == 1023) total[b] = s[1023];
+}
+
+// every in-frame corner into its target's bucket, in arrival order: {source*4 + corner, weight bits, global target, 0}
+template <int MODE>
+__global__ __launch_bounds__(256) void k_ord_place(const float* __restrict__ flow, const float* __restrict__ valid, int H, int W,
+                                                   int* __restrict__ cursor, int4* __restrict__ slots) {
+    const int b = blockIdx.y, HW = H * W;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= HW) return;
+    int tnw;
+    float w[4];
+    const int m = ord_corners<MODE>(flow, valid, b, p, H, W, tnw, w);
+    const int lim = (b + 1) * 4 * HW;            // the batch element's slot range (count and place apply the same rules)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (!(m & (1 << k))) continue;
+        const int gt = b * HW + ord_target(tnw, k, W);
+        const int pos = atomicAdd(cursor + gt, 1);
+        if (pos < lim) slots[pos] = make_int4(p * 4 + k, __float_as_int(w[k]), gt, 0);
+    }
+}
+
+// entry -> sorted position: its bucket's start + the number of the bucket's entries with a smaller source index
+__global__ __launch_bounds__(256) void k_ord_rank(const int4* __restrict__ slots, const int* __restrict__ start, const int* __restrict__ count,
+                                                  const int* __restrict__ total, int HW, int2* __restrict__ sorted) {
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= total[b]) return;
+    const int4 e = slots[(size_t)b * 4 * HW + i];
+    const int lo = start[e.z], n = count[e.z];
+    int r = 0;
+    for (int j = 0; j < n; ++j) r += slots[lo + j].x < e.x ? 1 : 0;
+    sorted[lo + r] = make_int2(e.x >> 2, e.y);
+}
+
+// the first ORD_REG entries of a bucket are held in registers across the channel loop
+#define ORD_REG 4
+
+// one channel plane's sum over a sorted bucket: acc = (((0 + t_0) + t_1) + ...), t_j = (v[src_j] * s_j) * w_j (MODE 1) or v[src_j] * w_j
+template <int MODE>
+__device__ __forceinline__ float ord_plane_sum(const float* __restrict__ plane, const float* __restrict__ sc, const int2* __restrict__ list,
+                                               int n, const int (&rs)[ORD_REG], const float (&rsc)[ORD_REG], const float (&rw)[ORD_REG]) {
+#pragma clang fp contract(off)
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < ORD_REG; ++j)
+        if (j < n) acc = acc + (MODE == 1 ? (plane[rs[j]] * rsc[j]) * rw[j] : plane[rs[j]] * rw[j]);
+    for (int j = ORD_REG; j < n; ++j) {
+        const int2 e = list[j];
+        const float v = MODE == 1 ? plane[e.x] * sc[e.x] : plane[e.x];
+        acc = acc + v * __int_as_float(e.y);
+    }
+    return acc;
+}
+
+template <int MODE>
+__device__ __forceinline__ void ord_load_regs(const float* __restrict__ sc, const int2* __restrict__ list, int n, int (&rs)[ORD_REG],
+                                              float (&rsc)[ORD_REG], float (&rw)[ORD_REG]) {
+#pragma unroll
+    for (int j = 0; j < ORD_REG; ++j) {
+        const int2 e = j < n ? list[j] : make_int2(0, 0);
+        rs[j] = e.x;
+        rw[j] = __int_as_float(e.y);
+        rsc[j] = (MODE == 1 && j < n) ? sc[e.x] : 0.f;
+    }
+}
+
+// MODE 0: out[b, c, t] = ordered sum (tcs_softsplat_sum_ordered).  64 consecutive targets per block, channel quarters per wave.
+__global__ __launch_bounds__(256) void k_ord_sum_gather(const int* __restrict__ start, const int* __restrict__ count,
+                                                        const int2* __restrict__ sorted, const float* __restrict__ in, int C, int HW,
+                                                        float* __restrict__ out) {
+    const int b = blockIdx.y, lane = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const int p = blockIdx.x * 64 + lane;
+    if (p >= HW) return;
+    const int lo = start[(size_t)b * HW + p], n = count[(size_t)b * HW + p];
+    const int2* list = sorted + lo;
+    int rs[ORD_REG];
+    float rsc[ORD_REG], rw[ORD_REG];
+    ord_load_regs<0>(nullptr, list, n, rs, rsc, rw);
+    const int cq = (C + 3) / 4, c_lo = q * cq, c_hi = min(C, c_lo + cq);
+    for (int c = c_lo; c < c_hi; ++c)
+        out[((size_t)b * C + c) * HW + p] = ord_plane_sum<0>(in + ((size_t)b * C + c) * HW, nullptr, list, n, rs, rsc, rw);
+}
+
+// MODE 1: the ordered sums of warp() + k_warp_finish's normalisation, split and cosine cost, in k_warp_finish's layout and arithmetic.
+// Channel order of the sums as k_splat's accumulator: [0,C) prev_fmap * s, C the new disparity * s, C+1 the normaliser s.
+__global__ __launch_bounds__(256) void k_ord_warp_gather(const int* __restrict__ start, const int* __restrict__ count,
+                                                         const int2* __restrict__ sorted, const float* __restrict__ prev_fmap,
+                                                         const float* __restrict__ cur_disp, const float* __restrict__ scale,
+                                                         const float* __restrict__ cur_fmap, int C, int HW, float* __restrict__ out_disp,
+                                                         float* __restrict__ out_fmap, float* __restrict__ out_mask, float* __restrict__ out_cost) {
+#pragma clang fp contract(off)
+    __shared__ float s_part[3][4][64];
+    const int b = blockIdx.y, lane = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const int p_raw = blockIdx.x * 64 + lane;
+    const bool active = p_raw < HW;
+    const int p = active ? p_raw : HW - 1;
+    const int lo = start[(size_t)b * HW + p], n = count[(size_t)b * HW + p];
+    const int2* list = sorted + lo;
+    const float* sc = scale + (size_t)b * HW;
+    int rs[ORD_REG];
+    float rsc[ORD_REG], rw[ORD_REG];
+    ord_load_regs<1>(sc, list, n, rs, rsc, rw);
+    // normaliser (v = s) and disparity (v = cur_disp * s), summed in the same order as every other channel
+    float norm = 0.f;
+#pragma unroll
+    for (int j = 0; j < ORD_REG; ++j)
+        if (j < n) norm = norm + rsc[j] * rw[j];
+    for (int j = ORD_REG; j < n; ++j) norm = norm + sc[list[j].x] * __int_as_float(list[j].y);
+    const float mask = (norm != 0.f) ? 1.f : 0.f;
+    const float den = fmaxf(norm, 1e-7f);
+    if (q == 0 && active) {
+        out_disp[(size_t)b * HW + p] = ord_plane_sum<1>(cur_disp + (size_t)b * HW, sc, list, n, rs, rsc, rw) / den;
+        out_mask[(size_t)b * HW + p] = mask;
+    }
+    const int cq = (C + 3) / 4, c_lo = q * cq, c_hi = min(C, c_lo + cq);
+    float dot = 0.f, n1 = 0.f, nw = 0.f;
+    for (int c = c_lo; c < c_hi; ++c) {
+        const float fw = ord_plane_sum<1>(prev_fmap + ((size_t)b * C + c) * HW, sc, list, n, rs, rsc, rw) / den;
+        if (out_fmap && active) out_fmap[((size_t)b * C + c) * HW + p] = fw;
+        if (out_cost) {
+            const float f1 = cur_fmap[((size_t)b * C + c) * HW + p];
+            dot = fmaf(f1, fw, dot);
+            n1 = fmaf(f1, f1, n1);
+            nw = fmaf(fw, fw, nw);
+        }
+    }
+    if (!out_cost) return;
+    s_part[0][q][lane] = dot; s_part[1][q][lane] = n1; s_part[2][q][lane] = nw;
+    __syncthreads();
+    if (q == 0 && active) {
+        float t[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) t[k] = ((s_part[k][0][lane] + s_part[k][1][lane]) + s_part[k][2][lane]) + s_part[k][3][lane];
+        out_cost[(size_t)b * HW + p] = t[0] / (fmaxf(sqrtf(t[1]), 1e-12f) * fmaxf(sqrtf(t[2]), 1e-12f)) * mask;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // backward grid (geo_utils.py:201-236)
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_backward_grid(const float* __restrict__ disp, const float* __restrict__ T_rel,
@@ -332,7 +550,62 @@ static WarpWs carve(void* ws, int B, int C, int H, int W) {
     return w;
 }
 
+// the inverted index of the ordered splat; `scale` only for warp()
+struct OrdWs {
+    int *count, *start, *cursor, *total;
+    int4* slots;
+    int2* sorted;
+    float* scale;
+    size_t count_bytes;
+};
+
+static size_t ord_bytes(int B, size_t HW, bool with_scale) {
+    const size_t n = (size_t)B * HW;
+    return al256(n * 4) * 3 + al256((size_t)B * 4) + al256(4 * n * sizeof(int4)) + al256(4 * n * sizeof(int2)) + (with_scale ? al256(n * 4) : 0);
+}
+
+static OrdWs carve_ord(void* ws, int B, size_t HW, bool with_scale) {
+    const size_t n = (size_t)B * HW;
+    char* p = reinterpret_cast<char*>(ws);
+    OrdWs o;
+    o.count = reinterpret_cast<int*>(p);    o.count_bytes = al256(n * 4); p += o.count_bytes;
+    o.start = reinterpret_cast<int*>(p);    p += al256(n * 4);
+    o.cursor = reinterpret_cast<int*>(p);   p += al256(n * 4);
+    o.total = reinterpret_cast<int*>(p);    p += al256((size_t)B * 4);
+    o.slots = reinterpret_cast<int4*>(p);   p += al256(4 * n * sizeof(int4));
+    o.sorted = reinterpret_cast<int2*>(p);  p += al256(4 * n * sizeof(int2));
+    o.scale = with_scale ? reinterpret_cast<float*>(p) : nullptr;
+    return o;
+}
+
+// the B*4*HW slot positions and source*4 + corner keys are ints; the scan runs one block per batch element
+static bool ord_dims_ok(int B, int H, int W) { return (long long)B * 4 * H * W <= 0x7fffffffLL && B <= 65535; }
+
+// count -> scan -> place -> rank for a splat along `flow`; MODE 1 also fills o.scale
+template <int MODE>
+static void ord_index(const float* flow, const float* cur_disp, const float* valid, const float* mean, int B, int H, int W, const OrdWs& o,
+                      hipStream_t s) {
+    const int HW = H * W, nb = tcs_cdiv(HW, 256);
+    const size_t n4 = o.count_bytes / 16;
+    hipLaunchKernelGGL(k_zero_fill, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<float4*>(o.count), n4);
+    hipLaunchKernelGGL(k_ord_count<MODE>, dim3(nb, B), dim3(256), 0, s, flow, cur_disp, valid, mean, H, W, o.count, o.scale);
+    hipLaunchKernelGGL(k_ord_scan, dim3(B), dim3(1024), 0, s, o.count, HW, o.start, o.cursor, o.total);
+    hipLaunchKernelGGL(k_ord_place<MODE>, dim3(nb, B), dim3(256), 0, s, flow, valid, H, W, o.cursor, o.slots);
+    hipLaunchKernelGGL(k_ord_rank, dim3(tcs_cdiv(4LL * HW, 256), B), dim3(256), 0, s, o.slots, o.start, o.count, o.total, HW, o.sorted);
+}
+
 extern "C" {
+
+size_t tcs_warp_ordered_workspace_bytes(int B, int C, int H, int W) {
+    if (B <= 0 || C < 0 || H <= 0 || W <= 0) return 0;
+    const size_t HW = (size_t)H * W;
+    return al256(B * HW * 4) * 2 + al256(2 * B * HW * 4) + al256((size_t)B * tcs_cdiv(HW, 256) * 4) + 256 + ord_bytes(B, HW, true);
+}
+
+size_t tcs_softsplat_ordered_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    return ord_bytes(B, (size_t)H * W, false);
+}
 
 size_t tcs_warp_workspace_bytes(int B, int C, int H, int W) {
     if (B <= 0 || C < 0 || H <= 0 || W <= 0) return 0;
@@ -397,6 +670,37 @@ int tcs_softsplat_sum(const float* in, const float* flow, int B, int C, int H, i
     const int cpg = 16, groups = tcs_cdiv(C, cpg);
     hipLaunchKernelGGL(k_splat<0>, dim3(nb, B, groups), dim3(256), 0, tcs_stream(stream), in, flow,
                        (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, C, H, W, cpg, out);
+    return tcs_launch_status();
+}
+
+int tcs_warp_forward_ordered(const float* prev_disp, const float* prev_fmap, const float* T_rel, const float* K,
+                             const float* K_inv, const float* baseline, int B, int C, int H, int W,
+                             float* out_disp, float* out_fmap, float* out_mask, const float* cur_fmap, float* out_cost,
+                             void* workspace, tcs_stream_t stream) {
+    if (!prev_disp || !prev_fmap || !T_rel || !K || !K_inv || !baseline || !out_disp || !out_mask || !workspace)
+        return TCS_EINVAL;
+    if ((cur_fmap == nullptr) != (out_cost == nullptr)) return TCS_EINVAL;
+    if (B <= 0 || B > 65535 || C <= 0 || H <= 0 || W <= 0 || !ord_dims_ok(B, H, W)) return TCS_EINVAL;
+    hipStream_t s = tcs_stream(stream);
+    const WarpWs w = carve(workspace, B, C, H, W);
+    int rc = geometry(prev_disp, T_rel, K, K_inv, baseline, B, H, W, w, s);
+    if (rc) return rc;
+    const OrdWs o = carve_ord(w.acc, B, (size_t)H * W, true);          // the ordered index sits where the atomic path's accumulator does
+    ord_index<1>(w.flow, w.cur_disp, w.valid, w.mean, B, H, W, o, s);
+    hipLaunchKernelGGL(k_ord_warp_gather, dim3(tcs_cdiv((long long)H * W, 64), B), dim3(256), 0, s, o.start, o.count, o.sorted, prev_fmap,
+                       w.cur_disp, o.scale, cur_fmap, C, H * W, out_disp, out_fmap, out_mask, out_cost);
+    return tcs_launch_status();
+}
+
+int tcs_softsplat_sum_ordered(const float* in, const float* flow, int B, int C, int H, int W, float* out, void* workspace,
+                              tcs_stream_t stream) {
+    if (!in || !flow || !out || !workspace || B <= 0 || B > 65535 || C <= 0 || H <= 0 || W <= 0 || !ord_dims_ok(B, H, W))
+        return TCS_EINVAL;
+    hipStream_t s = tcs_stream(stream);
+    const OrdWs o = carve_ord(workspace, B, (size_t)H * W, false);
+    ord_index<0>(flow, nullptr, nullptr, nullptr, B, H, W, o, s);
+    hipLaunchKernelGGL(k_ord_sum_gather, dim3(tcs_cdiv((long long)H * W, 64), B), dim3(256), 0, s, o.start, o.count, o.sorted, in, C, H * W,
+                       out);
     return tcs_launch_status();
 }
 

@@ -81,6 +81,11 @@ SIGNATURES = {
                                  c_fp, c_fp]),
     "tcs_warp_geometry": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "tcs_softsplat_sum": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp]),
+    "tcs_warp_ordered_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
+    "tcs_warp_forward_ordered": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp,
+                                         c_fp, c_fp]),
+    "tcs_softsplat_ordered_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
+    "tcs_softsplat_sum_ordered": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp]),
     "tcs_backward_grid": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp]),
     "tcs_bilinear_sample": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp]),
     "tcs_grid_halve": (c_int, [c_fp, c_int, c_int, c_int, c_fp, c_fp]),

@@ -144,21 +144,25 @@ def _cam(T_rel, K, K_inv, baseline, B):
     return T_rel, K, K_inv, baseline
 
 
-def warp_forward(prev_disp, prev_fmap, T_rel, K, K_inv, baseline, cur_fmap=None, want_fmap=True):
-    """-> (disp [B,1,H,W], fmap [B,C,H,W] or None, mask [B,1,H,W], cost [B,1,H,W] or None)"""
+def warp_forward(prev_disp, prev_fmap, T_rel, K, K_inv, baseline, cur_fmap=None, want_fmap=True, ordered=False):
+    """-> (disp [B,1,H,W], fmap [B,C,H,W] or None, mask [B,1,H,W], cost [B,1,H,W] or None)
+    ordered: the splat sums in a fixed order (tcs_warp_forward_ordered), so the outputs are bit-reproducible from run to run;
+    False is the float-atomic splat (tcs_warp_forward)."""
     B, Cc, H, W = _dims4(prev_fmap, "prev_fmap")
     if tuple(prev_disp.shape) != (B, 1, H, W):
         raise ValueError("prev_disp must be [B,1,H,W] matching prev_fmap")
     T_rel, K, K_inv, baseline = _cam(T_rel, K, K_inv, baseline, B)
     L = nv.lib()
-    ws = torch.empty(L.tcs_warp_workspace_bytes(B, Cc, H, W) // 4, dtype=torch.float32, device=prev_fmap.device)
+    ws_bytes, fn, name = ((L.tcs_warp_ordered_workspace_bytes, L.tcs_warp_forward_ordered, "tcs_warp_forward_ordered") if ordered else
+                          (L.tcs_warp_workspace_bytes, L.tcs_warp_forward, "tcs_warp_forward"))
+    ws = torch.empty(ws_bytes(B, Cc, H, W) // 4, dtype=torch.float32, device=prev_fmap.device)
     o_disp, o_mask = _new(prev_disp, B, 1, H, W), _new(prev_disp, B, 1, H, W)
     o_fmap = _new(prev_fmap, B, Cc, H, W) if want_fmap else None
     o_cost = _new(prev_disp, B, 1, H, W) if cur_fmap is not None else None
-    rc = L.tcs_warp_forward(nv.ptr(prev_disp, "prev_disp"), nv.ptr(prev_fmap, "prev_fmap"), nv.ptr(T_rel), nv.ptr(K), nv.ptr(K_inv),
-                            nv.ptr(baseline), B, Cc, H, W, nv.ptr(o_disp), nv.ptr(o_fmap), nv.ptr(o_mask),
-                            nv.ptr(cur_fmap, "cur_fmap"), nv.ptr(o_cost), nv.ptr(ws), nv.stream())
-    nv.check(rc, "tcs_warp_forward")
+    rc = fn(nv.ptr(prev_disp, "prev_disp"), nv.ptr(prev_fmap, "prev_fmap"), nv.ptr(T_rel), nv.ptr(K), nv.ptr(K_inv),
+            nv.ptr(baseline), B, Cc, H, W, nv.ptr(o_disp), nv.ptr(o_fmap), nv.ptr(o_mask),
+            nv.ptr(cur_fmap, "cur_fmap"), nv.ptr(o_cost), nv.ptr(ws), nv.stream())
+    nv.check(rc, name)
     return o_disp, o_fmap, o_mask, o_cost
 
 
@@ -175,10 +179,18 @@ def warp_geometry(prev_disp, T_rel, K, K_inv, baseline):
     return cd, va, fl, me
 
 
-def softsplat_sum(inp, flow):
+def softsplat_sum(inp, flow, ordered=False):
+    """Summation splat of `inp` along `flow`.  ordered: fixed summation order (tcs_softsplat_sum_ordered, bit-reproducible)."""
     B, Cc, H, W = _dims4(inp, "tenIn")
     if tuple(flow.shape) != (B, 2, H, W):
         raise ValueError("tenFlow must be [B,2,H,W]")
+    if ordered:
+        L = nv.lib()
+        out = torch.empty_like(inp)
+        ws = torch.empty(L.tcs_softsplat_ordered_workspace_bytes(B, H, W) // 4, dtype=torch.float32, device=inp.device)
+        nv.check(L.tcs_softsplat_sum_ordered(nv.ptr(inp, "tenIn"), nv.ptr(flow, "tenFlow"), B, Cc, H, W, nv.ptr(out), nv.ptr(ws),
+                                             nv.stream()), "tcs_softsplat_sum_ordered")
+        return out
     out = torch.zeros_like(inp)
     nv.check(nv.lib().tcs_softsplat_sum(nv.ptr(inp, "tenIn"), nv.ptr(flow, "tenFlow"), B, Cc, H, W, nv.ptr(out), nv.stream()),
              "tcs_softsplat_sum")
