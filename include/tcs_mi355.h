@@ -36,7 +36,8 @@ extern "C" {
 typedef void* tcs_stream_t;
 
 int tcs_abi_version(void);                 /* bumped when a signature changes (7: grouped launches, blend_warm_*; 8: `products`, the
-                                              last field of tcs_conv_desc and tcs_conv_s16_desc; 9: the ordered splat entry points) */
+                                              last field of tcs_conv_desc and tcs_conv_s16_desc; 9: the ordered splat entry points;
+                                              10: tcs_conv2d_group_fused) */
 const char* tcs_error_string(int code);
 
 /* ------------------------------------------------------------------------------------------------
@@ -310,8 +311,11 @@ int tcs_conv3x3_cout1(const float* x, const float* w_oihw, const float* bias, in
 int tcs_conv2d(const tcs_conv_desc* desc, tcs_stream_t stream);
 /* n (1 or 2) INDEPENDENT convolutions of tcs_conv2d as one launch where a grouped kernel exists for them (two fp32-MFMA 3x3 layers of
  * <= 32-channel tiles: the first layers of DispGradPredictor's stems, core/update.py:200-205), otherwise one after the other; bit-equal
- * to n calls of tcs_conv2d either way (see tcs_conv2d_s16_group). */
+ * to n calls of tcs_conv2d either way (see tcs_conv2d_s16_group).  Layers without a planned kernel (fp16-split, 7x7, Cin == 1) are
+ * launched while the pair is planned, ahead of the other layer.  tcs_conv2d_group_fused: 1 when the two descriptors would run as one
+ * launch (no launch is made, also not for the layers without a planned kernel: they answer 0). */
 int tcs_conv2d_group(const tcs_conv_desc* const* descs, int n, tcs_stream_t stream);
+int tcs_conv2d_group_fused(const tcs_conv_desc* const* descs, int n);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * Pre-split activations ("S16" tensors): the refinement loop's internal activation format.

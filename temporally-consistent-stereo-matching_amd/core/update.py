@@ -579,10 +579,8 @@ class DispGradPredictor(nn.Module):
         """fp32 API (update.py:198-214): -> (refined gradient [N,2,H,W], context [N,64,H,W]).  `g5`, when given, is
         5*disp_grad already produced by the gradient kernel; `cands` the gradient candidates of `disp`."""
         disp = disp.float().contiguous()
-        if g5 is None:
-            g5 = (5 * disp_grad).float().contiguous()            # update.py:199
-        if cands is None:
-            cands = ops.grad_candidates(disp)                    # [N,32,H,W] (update.py:202-204)
+        g5 = (5 * disp_grad if g5 is None else g5).float().contiguous()          # update.py:199
+        cands = (ops.grad_candidates(disp) if cands is None else cands).float().contiguous()    # [N,32,H,W] (update.py:202-204)
         pool = pool_of(self)
         c16 = [to16(pool, c, (id(self), "clist_in", i)) for i, c in enumerate(clist)]
         grad, ctx = self.run(pool, g5, cands, self.prepare(pool, c16))

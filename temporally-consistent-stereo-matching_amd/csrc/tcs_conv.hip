@@ -304,11 +304,15 @@ __global__ __launch_bounds__(256) void k_pack_weight(const float* __restrict__ w
 // a launch that tcs_conv2d_group has asked to be planned instead of issued (tcs_conv_s16.hip: S16Plan)
 struct ConvPlan {
     bool filled;
+    bool query;                     // tcs_conv2d_group_fused: the launches without a planner return instead of launching
     int key;                        // KS * 10000 + MT * 1000 + KC * 10 + EPI
     ConvArgs args;
     int (*launch_alone)(const ConvArgs&, hipStream_t);
 };
 static thread_local ConvPlan* g_conv_plan = nullptr;
+
+// tcs_conv2d_group_fused asks which kernel a descriptor would take: the launches without a planner must not happen
+static inline bool conv_query_only() { return g_conv_plan && g_conv_plan->query; }
 
 template <int KS, int MT, int KC, int EPI>
 static int launch_mfma(const ConvArgs& a, hipStream_t s) {
@@ -421,6 +425,7 @@ int tcs_conv2d(const tcs_conv_desc* d, tcs_stream_t stream) {
         a.w_unscale = d->weight_unscale;
         a.w_bytes = (int)(tcs_conv_packed_floats_f16x3(d->Cout, d->Cin, d->ksize) * sizeof(float));
         a.npx = tcs_cdiv(a.W, 32);
+        if (conv_query_only()) return TCS_OK;
         return tcs_conv_f16x3_launch(a, d->ksize, d->epilogue, stride, nprod, s);
     }
     if (d->math != TCS_MATH_F32) return TCS_EINVAL;
@@ -429,6 +434,7 @@ int tcs_conv2d(const tcs_conv_desc* d, tcs_stream_t stream) {
     if (d->epilogue == TCS_EPI_LINEAR) {
         if (d->out && (d->out_ctot < d->out_coff + d->Cout || d->out_coff < 0)) return TCS_EINVAL;
         if (d->Cin == 1) {
+            if (conv_query_only()) return TCS_OK;
             const dim3 grid(tcs_cdiv((long long)d->H * d->W, 256), d->B, tcs_cdiv(d->Cout, 16));
             if (d->ksize == 1) hipLaunchKernelGGL(k_conv_cin1<1>, grid, dim3(256), 0, s, a);
             else if (d->ksize == 3) hipLaunchKernelGGL(k_conv_cin1<3>, grid, dim3(256), 0, s, a);
@@ -442,6 +448,7 @@ int tcs_conv2d(const tcs_conv_desc* d, tcs_stream_t stream) {
         if (d->ksize == 3) return launch_by_tile<3, TCS_EPI_LINEAR>(a, nt, s);
         if (d->ksize == 1) return launch_by_tile<1, TCS_EPI_LINEAR>(a, nt, s);
         if (d->ksize == 7 && d->Cin == 3 && d->n_src == 1 && d->act != TCS_ACT_RELU_ADD_RELU) {   // RGB stem
+            if (conv_query_only()) return TCS_OK;
             const dim3 g7(tcs_cdiv(d->W, 64) * tcs_cdiv(d->H, 4), d->B, tcs_cdiv(d->Cout, 8));
             hipLaunchKernelGGL(k_conv7x7<3>, g7, dim3(256), 0, s, a);
             return tcs_launch_status();
@@ -467,20 +474,26 @@ int tcs_conv2d(const tcs_conv_desc* d, tcs_stream_t stream) {
     return TCS_EINVAL;
 }
 
+// the one pair instance: two 3x3 layers on the 32-wide tile, linear epilogue, same batch size
+static bool conv_pair_fusable(const ConvPlan* plan) {
+    constexpr int key = 3 * 10000 + 1 * 1000 + 16 * 10 + TCS_EPI_LINEAR;
+    return plan[0].filled && plan[1].filled && plan[0].key == key && plan[1].key == key && plan[0].args.B == plan[1].args.B;
+}
+
 int tcs_conv2d_group(const tcs_conv_desc* const* descs, int n, tcs_stream_t stream) {
     if (!descs || n < 1 || n > 2) return TCS_EINVAL;
     if (n == 1) return tcs_conv2d(descs[0], stream);
     ConvPlan plan[2];
     for (int i = 0; i < 2; ++i) {
         plan[i].filled = false;
+        plan[i].query = false;
         g_conv_plan = &plan[i];
         const int rc = tcs_conv2d(descs[i], stream);      // kernels without a planner (fp16-split, 7x7, single-channel) launch right here
         g_conv_plan = nullptr;
         if (rc != TCS_OK) return rc;
     }
     hipStream_t s = tcs_stream(stream);
-    constexpr int key = 3 * 10000 + 1 * 1000 + 16 * 10 + TCS_EPI_LINEAR;
-    if (plan[0].filled && plan[1].filled && plan[0].key == key && plan[1].key == key && plan[0].args.B == plan[1].args.B) {
+    if (conv_pair_fusable(plan)) {
         constexpr size_t lds = ((size_t)((16 * 6 * 34 + 3) & ~3) + (size_t)16 * 9 * 32) * sizeof(float);
         const int n0 = plan[0].args.npatch * plan[0].args.nct, n1 = plan[1].args.npatch * plan[1].args.nct;
         hipLaunchKernelGGL((k_conv_mfma_pair<3, 1, 16, TCS_EPI_LINEAR>), dim3(n0 + n1, plan[0].args.B), dim3(256), lds, s, plan[0].args,
@@ -493,6 +506,21 @@ int tcs_conv2d_group(const tcs_conv_desc* const* descs, int n, tcs_stream_t stre
         if (r != TCS_OK) return r;
     }
     return TCS_OK;
+}
+
+int tcs_conv2d_group_fused(const tcs_conv_desc* const* descs, int n) {
+    // diagnostic: 1 when tcs_conv2d_group would issue these descriptors as ONE launch; nothing is launched
+    if (!descs || n != 2) return 0;
+    ConvPlan plan[2];
+    for (int i = 0; i < 2; ++i) {
+        plan[i].filled = false;
+        plan[i].query = true;
+        g_conv_plan = &plan[i];
+        const int rc = tcs_conv2d(descs[i], nullptr);
+        g_conv_plan = nullptr;
+        if (rc != TCS_OK || !plan[i].filled) return 0;
+    }
+    return conv_pair_fusable(plan) ? 1 : 0;
 }
 
 }  // extern "C"

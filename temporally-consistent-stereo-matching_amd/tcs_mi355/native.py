@@ -108,6 +108,7 @@ SIGNATURES = {
     "tcs_conv3x3_cout1": (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp]),
     "tcs_conv2d": (c_int, [C.POINTER(ConvDesc), c_fp]),
     "tcs_conv2d_group": (c_int, [C.POINTER(C.POINTER(ConvDesc)), c_int, c_fp]),
+    "tcs_conv2d_group_fused": (c_int, [C.POINTER(C.POINTER(ConvDesc)), c_int]),
     "tcs_s16_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
     "tcs_s16_flags": (c_int, [C.POINTER(C.c_uint)]),
     "tcs_s16_flags_detail": (c_int, [C.POINTER(C.c_uint)]),

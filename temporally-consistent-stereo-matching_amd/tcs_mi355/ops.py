@@ -434,16 +434,18 @@ def _desc(pc: PackedConv, srcs: Sequence[torch.Tensor]) -> nv.ConvDesc:
     return d
 
 
-_GROUP = None            # descriptors of the `with grouped():` block being recorded (LINEAR tcs_conv2d launches)
+_GROUP = None            # (descriptor, name, tensors it points to) of the `with grouped():` block being recorded (LINEAR tcs_conv2d launches)
 
 
 class grouped:
     """`with ops.grouped(): conv2d(...); conv2d(...)` — two INDEPENDENT tcs_conv2d layers issued as one launch at the end of the block
     where the library has a grouped kernel for them (tcs_conv2d_group), otherwise one after the other; same results either way.
-    The fp32-tensor counterpart of tcs_mi355.s16.grouped."""
+    The fp32-tensor counterpart of tcs_mi355.s16.grouped.  A recorded descriptor holds raw pointers only, so the block keeps every
+    tensor the call was given (a temporary such as `x.contiguous()` included) alive until the launch."""
 
-    def __init__(self, enabled: bool = True):
-        self.enabled = enabled
+    def __init__(self, enabled: bool = True, report: bool = False):
+        self.enabled, self.report = enabled, report
+        self.fused: List[bool] = []          # with `report`: per pair, whether the library issued it as one launch
 
     def __enter__(self):
         global _GROUP
@@ -462,14 +464,17 @@ class grouped:
             return False
         for i in range(0, len(descs), 2):
             chunk = descs[i:i + 2]
-            arr = (C.POINTER(nv.ConvDesc) * len(chunk))(*[C.pointer(d) for d, _ in chunk])
-            nv.check(nv.lib().tcs_conv2d_group(arr, len(chunk), nv.stream()), "tcs_conv2d_group[" + " | ".join(n for _, n in chunk) + "]")
+            arr = (C.POINTER(nv.ConvDesc) * len(chunk))(*[C.pointer(d) for d, _, _ in chunk])
+            if self.report:
+                self.fused.append(len(chunk) == 2 and bool(nv.lib().tcs_conv2d_group_fused(arr, 2)))
+            nv.check(nv.lib().tcs_conv2d_group(arr, len(chunk), nv.stream()), "tcs_conv2d_group[" + " | ".join(n for _, n, _ in chunk) + "]")
         return False
 
 
-def _launch_conv(d, name: str):
+def _launch_conv(d, name: str, keep: tuple):
+    """tcs_conv2d now, or at the end of the enclosing `grouped()` block; `keep`: the objects whose memory `d` points to."""
     if _GROUP is not None:
-        _GROUP.append((d, name))
+        _GROUP.append((d, name, keep))
     else:
         nv.check(nv.lib().tcs_conv2d(C.byref(d), nv.stream()), name)
 
@@ -496,7 +501,7 @@ def conv2d(pc: PackedConv, srcs: Sequence[torch.Tensor], act: str = "none", adde
         d.epilogue, d.act, d.post_scale = EPI_LINEAR, ACT[act], float(post_scale)
         d.addend = nv.ptr(addend, "addend")
         d.out16, d.out16_groups, d.out16_group_offset = out16.ptr(), out16.G, int(out16_group_offset)
-        _launch_conv(d, "tcs_conv2d[s16 out]")
+        _launch_conv(d, "tcs_conv2d[s16 out]", (pc, srcs, addend, out16, image_pair))
         return out16
     if stride not in (1, 2):
         raise ValueError("stride 1 or 2")
@@ -513,7 +518,7 @@ def conv2d(pc: PackedConv, srcs: Sequence[torch.Tensor], act: str = "none", adde
     d.epilogue, d.act, d.post_scale = EPI_LINEAR, ACT[act], float(post_scale)
     d.addend = nv.ptr(addend, "addend")
     d.out, d.out_ctot, d.out_coff = nv.ptr(out, "out"), int(out.shape[1]), int(out_coff)
-    _launch_conv(d, "tcs_conv2d")
+    _launch_conv(d, "tcs_conv2d", (pc, srcs, addend, out, image_pair))
     return out
 
 

@@ -28,7 +28,7 @@ def groups_for(C_: int) -> int:
 
 
 # ---- grouped launches (tcs_conv2d_s16_group) -------------------------------------------------------------------------
-_GROUP: Optional[list] = None        # descriptors of the `with grouped():` block being recorded
+_GROUP: Optional[list] = None        # (descriptor, name, tensors it points to) of the `with grouped():` block being recorded
 
 
 class grouped:
@@ -36,7 +36,8 @@ class grouped:
     INDEPENDENT layers (neither reads what the other writes) and go out as one launch at the end of the block where the library
     has a pair kernel for their tile instances, otherwise one after the other; the tensors the calls return are valid after the
     block.  What this replaces is a fork / join of two graph branches (tcs_mi355/streams.py): the pair keeps the concurrency
-    without the cross-queue dependencies.  `enabled=False` (A/B runs): launches happen at once, as without the block."""
+    without the cross-queue dependencies.  `enabled=False` (A/B runs): launches happen at once, as without the block.  A recorded
+    descriptor holds raw pointers only, so the block keeps every tensor the call was given (temporaries included) alive until the launch."""
 
     def __init__(self, enabled: bool = True, report: bool = False):
         self.enabled, self.report = enabled, report
@@ -59,17 +60,17 @@ class grouped:
             return False
         for i in range(0, len(descs), 2):
             chunk = descs[i:i + 2]
-            arr = (C.POINTER(nv.ConvS16Desc) * len(chunk))(*[C.pointer(d) for d, _ in chunk])
+            arr = (C.POINTER(nv.ConvS16Desc) * len(chunk))(*[C.pointer(d) for d, _, _ in chunk])
             if self.report:
                 self.fused.append(len(chunk) == 2 and bool(nv.lib().tcs_conv2d_s16_group_fused(arr, 2)))
-            nv.check(nv.lib().tcs_conv2d_s16_group(arr, len(chunk), nv.stream()), "tcs_conv2d_s16_group[" + " | ".join(n for _, n in chunk) + "]")
+            nv.check(nv.lib().tcs_conv2d_s16_group(arr, len(chunk), nv.stream()), "tcs_conv2d_s16_group[" + " | ".join(n for _, n, _ in chunk) + "]")
         return False
 
 
-def _launch(d, name: str):
-    """tcs_conv2d_s16 now, or at the end of the enclosing `grouped()` block."""
+def _launch(d, name: str, keep: tuple):
+    """tcs_conv2d_s16 now, or at the end of the enclosing `grouped()` block; `keep`: the objects whose memory `d` points to."""
     if _GROUP is not None:
-        _GROUP.append((d, name))
+        _GROUP.append((d, name, keep))
     else:
         nv.check(nv.lib().tcs_conv2d_s16(C.byref(d), nv.stream()), name)
 
@@ -263,7 +264,7 @@ def conv2d(pc: PackedConv, srcs: Sequence[S16], act: str = "none", addend: Optio
     if out32 is not None:
         d.out32, d.out_ctot, d.out_coff = nv.ptr(out32, "out32"), int(out32.shape[1]), int(out_coff)
     d.tile_cfg = int(tile_cfg)
-    _launch(d, "tcs_conv2d_s16")
+    _launch(d, "tcs_conv2d_s16", (pc, srcs, addend, addend16, out16, out16b, out32, taps, tap_weights))
     return out16, out32
 
 
@@ -301,7 +302,7 @@ def deconv4x4s2(pc: PackedConv, srcs: Sequence[S16], out16: Optional[S16] = None
             raise ValueError("deconv4x4s2: `in_stats` must be an int64 tensor of [B, Cout, 2] (deconv_in_stats_workspace)")
         d.in_stats, d.in_eps = nv.ptr(in_stats, "in_stats", torch.int64), float(eps)
     d.tile_cfg = int(tile_cfg)
-    _launch(d, "tcs_conv2d_s16[deconv2x]")
+    _launch(d, "tcs_conv2d_s16[deconv2x]", (pc, srcs, out16, in_stats))
     return out16
 
 
@@ -338,7 +339,7 @@ def gru_gates(pc_zr: PackedConv, srcs: Sequence[S16], h: S16, cz=None, cr=None, 
     d.out32, d.out_ctot, d.out_coff = nv.ptr(z_out, "z"), hid, 0
     d.out16, d.out16_groups, d.out16_group_offset = rh_out.ptr(), rh_out.G, 0
     d.tile_cfg = int(tile_cfg)
-    _launch(d, "tcs_conv2d_s16[gru_zr]")
+    _launch(d, "tcs_conv2d_s16[gru_zr]", (pc_zr, srcs, h, cz, cr, z_out, rh_out))
     return z_out, rh_out
 
 
@@ -358,7 +359,7 @@ def gru_update(pc_q: PackedConv, srcs: Sequence[S16], h: S16, z: torch.Tensor, c
     if out32 is not None:
         d.out32, d.out_ctot, d.out_coff = nv.ptr(out32, "out32"), pc_q.cout, 0
     d.tile_cfg = int(tile_cfg)
-    _launch(d, "tcs_conv2d_s16[gru_q]")
+    _launch(d, "tcs_conv2d_s16[gru_q]", (pc_q, srcs, h, z, cq, out, out32))
     return out
 
 
@@ -526,7 +527,7 @@ def conv1x1_blend(pc: PackedConv, srcs: Sequence[S16], cand9, disp_q, coords1, f
             d.blend_warm_pyr[i] = nv.ptr(warm_pyramid.levels[i], "pyr")
         d.blend_warm_radius = int(warm_radius)
     d.tile_cfg = int(tile_cfg)
-    _launch(d, "tcs_conv2d_s16[blend9]")
+    _launch(d, "tcs_conv2d_s16[blend9]", (pc, srcs, cand9, disp_q, coords1, flow_x, flow_x_s16, refined, delta, warm_pyramid))
     return refined, delta
 
 

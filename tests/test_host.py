@@ -473,3 +473,40 @@ def test_lookup_profile_rows_are_selected_by_grid_size(tmp_path):
     assert "<4, 4>" in four["rocprof_loop_kernel"] and abs(four["rocprof_loop_avg_us"] - 9.254) < 1e-3
     assert abs(four["frac_rocprof_loop"] - 0.3195) < 2e-3 and abs(four["frac_rocprof_burst"] - 0.4934) < 2e-3
     assert "<4, 1>" in d["one_sequence_640x480"]["rocprof_loop_kernel"] and "<4, 1>" in d["kitti_375x1242"]["rocprof_loop_kernel"]
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="descriptors with fake device pointers: host-only check")
+def test_conv_group_fused_query_answers_on_the_host():
+    """The answers of tcs_conv2d_group_fused, computed on the host: the fp32-MFMA pair of DispGradPredictor's stems at 120x160 is one
+    launch; at batch 4 (32 -> 64 takes the 64-wide tile), with mismatched batches, or with a layer that has no planned kernel
+    (fp16-split, Cin == 1) it is two.  (This checks the answers only; that the query makes no launch is a property of the code in
+    tcs_conv2d, where every launch without a planner is preceded by conv_query_only().)  The descriptors carry fake device pointers,
+    so the test runs only where no GPU is visible."""
+    import ctypes as C
+
+    from tcs_mi355 import native
+    lib = native.lib()
+    fake = 0x10000                                      # never dereferenced: nothing is launched
+
+    def desc(cin, cout, B, H=120, W=160, math=0):
+        d = native.ConvDesc()
+        d.src[0], d.src_ch[0], d.n_src = fake, cin, 1
+        d.weight, d.out = fake, fake
+        d.B, d.H, d.W, d.Cin, d.Cout, d.ksize = B, H, W, cin, cout, 3
+        d.post_scale, d.out_ctot, d.math, d.weight_unscale = 1.0, cout, math, 1.0
+        return d
+
+    def fused(a, b):
+        arr = (C.POINTER(native.ConvDesc) * 2)(C.pointer(a), C.pointer(b))
+        return lib.tcs_conv2d_group_fused(arr, 2)
+
+    assert fused(desc(2, 32, 1), desc(32, 64, 1)) == 1
+    assert fused(desc(2, 32, 1, 61, 83), desc(32, 64, 1, 61, 83)) == 1
+    assert fused(desc(2, 32, 4), desc(32, 64, 4)) == 0
+    assert fused(desc(2, 32, 2), desc(32, 64, 1)) == 0
+    assert fused(desc(32, 32, 1, math=1), desc(2, 32, 1)) == 0
+    assert fused(desc(2, 32, 1), desc(32, 32, 1, math=1)) == 0
+    assert fused(desc(1, 32, 1), desc(2, 32, 1)) == 0
+    assert fused(desc(2, 32, 1), desc(2, 32, 1, 0, 160)) == 0      # invalid descriptor
+    arr = (C.POINTER(native.ConvDesc) * 1)(C.pointer(desc(2, 32, 1)))
+    assert lib.tcs_conv2d_group_fused(arr, 1) == 0
