@@ -37,7 +37,7 @@ typedef void* tcs_stream_t;
 
 int tcs_abi_version(void);                 /* bumped when a signature changes (7: grouped launches, blend_warm_*; 8: `products`, the
                                               last field of tcs_conv_desc and tcs_conv_s16_desc; 9: the ordered splat entry points;
-                                              10: tcs_conv2d_group_fused) */
+                                              10: tcs_conv2d_group_fused; 11: the *_mixed entry points) */
 const char* tcs_error_string(int code);
 
 /* ------------------------------------------------------------------------------------------------
@@ -131,6 +131,28 @@ int tcs_warp_forward_ordered(const float* prev_disp, const float* prev_fmap, con
                              float* out_disp, float* out_fmap, float* out_mask,
                              const float* cur_fmap, float* out_cost,
                              void* workspace, tcs_stream_t stream);
+/*
+ * Mixed batches (tcs_warp_forward_mixed, tcs_warp_forward_ordered_mixed): independent sequences on the batch dimension, some of which
+ * start on this frame.  start [B] (device, unsigned char): nonzero = batch element b begins a sequence.  Arguments and outputs as in
+ * tcs_warp_forward / _ordered (same workspace size queries), plus the mask and the first-frame prior prior_disp, prior_cost,
+ * prior_mask [B,1,H,W] (tcs_corr_build's sparse_* outputs; all three required).
+ *   A start element reads none of prev_disp, prev_fmap, T_rel, K, K_inv, baseline (they may hold anything, NaN included); it adds
+ *   nothing to the mean and no splat contributions (no index entries in the ordered path).  Its out_disp, out_mask and out_cost are
+ *   copied from the prior, its out_fmap (when requested) is 0.
+ *   A temporal element (start[b] == 0) gets the arithmetic of the non-mixed entry point, except that the softmax metric's mean is
+ *   over the temporal elements' pixels only: exactly warp() on the sub-batch of temporal elements.  With no temporal element no mean
+ *   is formed.  With an all-zero mask the outputs are bit-equal to tcs_warp_forward / _ordered on the same inputs.
+ */
+int tcs_warp_forward_mixed(const float* prev_disp, const float* prev_fmap, const float* T_rel, const float* K,
+                           const float* K_inv, const float* baseline, const unsigned char* start, const float* prior_disp,
+                           const float* prior_cost, const float* prior_mask, int B, int C, int H, int W,
+                           float* out_disp, float* out_fmap, float* out_mask, const float* cur_fmap, float* out_cost,
+                           void* workspace, tcs_stream_t stream);
+int tcs_warp_forward_ordered_mixed(const float* prev_disp, const float* prev_fmap, const float* T_rel, const float* K,
+                                   const float* K_inv, const float* baseline, const unsigned char* start, const float* prior_disp,
+                                   const float* prior_cost, const float* prior_mask, int B, int C, int H, int W,
+                                   float* out_disp, float* out_fmap, float* out_mask, const float* cur_fmap, float* out_cost,
+                                   void* workspace, tcs_stream_t stream);
 size_t tcs_softsplat_ordered_workspace_bytes(int B, int H, int W);
 int tcs_softsplat_sum_ordered(const float* in, const float* flow, int B, int C, int H, int W, float* out, void* workspace,
                               tcs_stream_t stream);
@@ -156,11 +178,19 @@ int tcs_backward_grid(const float* disp, const float* T_rel, const float* K, con
  * T_rel = T * inv(T_prev) (geo_utils.py:148-155) and T_back = T_prev * inv(T).  K [B,3,3], T [B,4,4]. */
 int tcs_pose_prepare(const float* K, const float* T, const float* T_prev, float scale, int B,
                      float* K_scaled, float* K_scaled_inv, float* T_rel, float* T_back, tcs_stream_t stream);
+/* The same for a mixed batch (start [B], device): start elements get identity T_rel / T_back without their T or T_prev being read;
+ * K_scaled and its inverse are formed for every element.  T, T_prev, T_rel, T_back are required. */
+int tcs_pose_prepare_mixed(const float* K, const float* T, const float* T_prev, const unsigned char* start, float scale, int B,
+                           float* K_scaled, float* K_scaled_inv, float* T_rel, float* T_back, tcs_stream_t stream);
 
 /* bilinear_sampler (core/utils/utils.py:82-97): img [B,C,Hi,Wi] sampled at grid [B,2,Ho,Wo] (x,y in
  * pixels), zeros outside, align_corners=True -> out [B,C,Ho,Wo]. */
 int tcs_bilinear_sample(const float* img, const float* grid, int B, int C, int Hi, int Wi, int Ho, int Wo,
                         float* out, tcs_stream_t stream);
+/* The same for a mixed batch (start [B], device): a start element's output is +0.0 everywhere (a first frame's warped hidden
+ * states), and neither its img nor its grid is read. */
+int tcs_bilinear_sample_mixed(const float* img, const float* grid, const unsigned char* start, int B, int C, int Hi, int Wi, int Ho,
+                              int Wo, float* out, tcs_stream_t stream);
 
 /* 0.5 * F.interpolate(grid, scale_factor=0.5, bilinear, align_corners=True) (tc_stereo.py:163):
  * grid [B,2,H,W] -> [B,2,H/2,W/2]. */

@@ -46,6 +46,32 @@ class autocast(contextlib.AbstractContextManager):
 HIP_PRECISIONS = {"fp32": 0, "fp16": 1}
 
 
+def sequence_starts(value, batch: int, device=None) -> torch.Tensor:
+    """`params["new_sequence"]` validated and normalised: a bool / uint8 tensor of shape [batch] (host or device) or a Python sequence
+    of `batch` bools -> a uint8 [batch] tensor on `device` (1 = the element begins a sequence).  A device tensor is converted on the
+    device and never read on the host.  Raises ValueError for a wrong length, a wrong dtype or a mask that is not 1-D."""
+    if torch.is_tensor(value):
+        if value.ndim != 1:
+            raise ValueError(f"new_sequence must be 1-D [{batch}], got shape {tuple(value.shape)}")
+        if value.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"new_sequence must be a bool or uint8 tensor, got {value.dtype}")
+        if int(value.shape[0]) != batch:
+            raise ValueError(f"new_sequence has {int(value.shape[0])} entries for batch {batch}")
+        t = value
+    else:
+        if isinstance(value, (str, bytes)) or not hasattr(value, "__len__"):
+            raise ValueError(f"new_sequence must be a tensor or a sequence of {batch} bools, got {type(value).__name__}")
+        vals = list(value)
+        if len(vals) != batch:
+            raise ValueError(f"new_sequence has {len(vals)} entries for batch {batch}")
+        if not all(isinstance(v, bool) or type(v).__name__ in ("bool", "bool_") for v in vals):      # (numpy bools too)
+            raise ValueError("new_sequence must hold bools (a nested or non-bool sequence is not a [B] mask)")
+        t = torch.tensor([bool(v) for v in vals], dtype=torch.uint8)
+    if device is not None and t.device != torch.device(device):
+        t = t.to(device)
+    return t.to(torch.uint8).contiguous()
+
+
 class TCStereo(nn.Module):
     def __init__(self, args):
         super().__init__()
@@ -161,7 +187,8 @@ class TCStereo(nn.Module):
         behind the frame in flight, so that its host-side launch work is done while the GPU is still busy with that frame (on this
         stack the stage cannot run BESIDE the loop on the GPU).  The next `forward` with the SAME image tensors
         (same objects, unmodified) picks the result up; any other call simply extracts again.  `first`: that frame will be called with
-        params=None (start of a sequence: the arg-max prior is then built with the correlation volume).  Call it right AFTER the
+        params=None (start of a sequence: the arg-max prior is then built with the correlation volume) or with
+        params["new_sequence"] present (a mixed batch, which always takes the arg-max).  Call it right AFTER the
         `forward` it follows.  `inputs_ready` is kept for callers of round 3's two-stream version and no longer changes anything when
         the stage runs on the caller's stream.  Results are identical with and without the call."""
         if not image1.is_cuda:
@@ -174,6 +201,13 @@ class TCStereo(nn.Module):
         K [b,3,3], T / previous_T [b,4,4] world->camera, baseline [b], last_disp (= previous 'flow_q'),
         last_net_list, fmap1.  Returns {'flow' [b,1,H,W] (negative disparity, clipped at 0),
         'flow_q' [b,1,H/4,W/4], 'net_list', 'fmap1'} (tc_stereo.py:96-244).
+
+        Mixed batches (independent sequences on the batch dimension that start at different frames): `params["new_sequence"]`, a
+        bool / uint8 [b] tensor (host or device) or a sequence of b bools.  With the key present (even all False) the frame takes the
+        mixed path: an element marked True is computed as a first frame (arg-max prior, zero warped hidden states) and its temporal
+        entries (previous_T, last_disp, last_net_list, fmap1; they must have the batch's shapes) are never read, so they may hold
+        anything; an element marked False gets what a temporal call on the sub-batch of the temporal elements gives (the warp's
+        metric mean covers their pixels only).  The mask is never read on the host.  Absent or None: exactly the temporal path.
 
         A frame is two fixed launch sequences with no host round trip — the image-only stage (`_extract_stage`) and the
         state-dependent stage (`_refine_stage`) — so by default each is captured once per (shape, iters, branch) into a HIP
@@ -188,11 +222,13 @@ class TCStereo(nn.Module):
         if params is not None:
             temporal = (params["K"], params["T"], params["previous_T"], params["baseline"], params["last_disp"],
                         list(params["last_net_list"]), params["fmap1"])
+            if params.get("new_sequence") is not None:          # mixed batch: the mask is the 8th entry
+                temporal = temporal + (sequence_starts(params["new_sequence"], int(image1.shape[0]), image1.device),)
         return self._pipeline()(image1, image2, iters, temporal, use_graph=self._graph_mode())
 
     def _frame(self, image1, image2, iters, temporal):
         """One frame as a pure launch sequence on the current stream (both stages back to back)."""
-        feats = self._extract_stage(image1, image2, temporal is None)
+        feats = self._extract_stage(image1, image2, temporal is None or len(temporal) == 8)
         return self._refine_loop(feats, self._refine_head(feats, temporal), iters)
 
     def _extract_stage(self, image1, image2, first):
@@ -238,19 +274,23 @@ class TCStereo(nn.Module):
         """The state-dependent head of a frame (tensors in, tensors out; capturable): prior from the arg-max or from the pose warp of the
         previous frame, disparity completion, hidden-state warp and fusion (tc_stereo.py:119-172) -> what the loop starts from."""
         first = temporal is None
+        start = temporal[7] if temporal is not None and len(temporal) == 8 else None     # mixed batch: uint8 [B] sequence starts
         fmap1, corr_fn = feats["fmap1"], feats["corr_fn"]
         net_list = feats["net_list"]
         if first:
             last_net_list = None
             sparse_disp, cost, sparse_mask = feats["prior"] if feats["prior"] is not None else corr_fn.argmax_disp()
         else:
-            K, T, previous_T, baseline, last_disp, last_net_list, last_fmap1 = temporal
-            # K_scale, its inverse, T @ inv(previous_T), previous_T @ inv(T): one tiny kernel, no host sync
-            K_scale, K_scale_inv, relative_T, back_T = ops.pose_prepare(K, T, previous_T, self.scale_rate)
+            K, T, previous_T, baseline, last_disp, last_net_list, last_fmap1 = temporal[:7]
+            # K_scale, its inverse, T @ inv(previous_T), previous_T @ inv(T): one tiny kernel, no host sync (identity poses for the
+            # start elements of a mixed batch)
+            K_scale, K_scale_inv, relative_T, back_T = ops.pose_prepare(K, T, previous_T, self.scale_rate, start=start)
+            # a mixed batch's start elements take the arg-max prior, selected inside the warp's finish kernel
+            prior = None if start is None else (feats["prior"] if feats["prior"] is not None else corr_fn.argmax_disp())
             # warp + normalise + cosine cost in one launch sequence; the warped feature map is never materialised
             sparse_disp, _, sparse_mask, cost = ops.warp_forward(
                 (-last_disp).float().contiguous(), last_fmap1.float().contiguous(), relative_T, K_scale,
-                K_scale_inv, baseline, cur_fmap=fmap1, want_fmap=False, ordered=self._hip_deterministic)
+                K_scale_inv, baseline, cur_fmap=fmap1, want_fmap=False, ordered=self._hip_deterministic, start=start, prior=prior)
 
         pool = self._s16pool
         s16_head = "dc32" not in _X
@@ -267,7 +307,7 @@ class TCStereo(nn.Module):
             grid = ops.backward_grid(disp_init, back_T, K_scale, K_scale_inv, baseline)
             warped = []
             for i, net in enumerate(last_net_list):
-                warped.append(ops.bilinear_sample(net.float().contiguous(), grid))
+                warped.append(ops.bilinear_sample(net.float().contiguous(), grid, start=start))   # (+0.0 for start elements)
                 if i + 1 < len(last_net_list):
                     grid = ops.grid_halve(grid)
 

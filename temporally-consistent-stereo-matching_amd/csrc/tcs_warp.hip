@@ -46,14 +46,28 @@ __device__ __forceinline__ void reproject(const Cam& c, float disp, float x, flo
 // ------------------------------------------------------------------------------------------------
 // forward geometry: new disparity, validity, forward flow, per-block partial sums of the disparity
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_warp_geometry(const float* __restrict__ disp, const float* __restrict__ T_rel,
-                                                       const float* __restrict__ K, const float* __restrict__ K_inv,
-                                                       const float* __restrict__ baseline, int H, int W,
-                                                       float* __restrict__ cur_disp, float* __restrict__ valid,
-                                                       float* __restrict__ flow, float* __restrict__ partial) {
+// MIXED (the *_mixed entry points): a batch element with start[b] != 0 begins a sequence.  It reads none of its inputs, writes
+// cur_disp = valid = flow = 0 (valid = 0: the splats skip it, atomic and ordered alike) and leaves exact zeros in its block partials.
+// The start branch leaves the kernel first (block-uniform), so that the code after it is the non-mixed kernel's, contraction included.
+template <bool MIXED>
+__device__ __forceinline__ void warp_geometry_body(const float* __restrict__ disp, const float* __restrict__ T_rel,
+                                                   const float* __restrict__ K, const float* __restrict__ K_inv,
+                                                   const float* __restrict__ baseline, const unsigned char* __restrict__ start,
+                                                   int H, int W, float* __restrict__ cur_disp, float* __restrict__ valid,
+                                                   float* __restrict__ flow, float* __restrict__ partial) {
     __shared__ float red[4];
     const int b = blockIdx.y, HW = H * W;
     const int p = blockIdx.x * 256 + threadIdx.x;
+    if (MIXED && start[b]) {
+        if (p < HW) {
+            cur_disp[(size_t)b * HW + p] = 0.f;
+            valid[(size_t)b * HW + p] = 0.f;
+            flow[((size_t)b * 2 + 0) * HW + p] = 0.f;
+            flow[((size_t)b * 2 + 1) * HW + p] = 0.f;
+        }
+        if (threadIdx.x == 0) partial[blockIdx.y * gridDim.x + blockIdx.x] = 0.f;
+        return;
+    }
     float cd = 0.f;
     if (p < HW) {
         const Cam c = load_cam(T_rel, K, K_inv, baseline, b);
@@ -72,15 +86,49 @@ __global__ __launch_bounds__(256) void k_warp_geometry(const float* __restrict__
     if (threadIdx.x == 0) partial[blockIdx.y * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// fixed-order reduction of the partial sums -> mean over ALL pixels of the batch (geo_utils.py:193)
-__global__ __launch_bounds__(256) void k_mean(const float* __restrict__ partial, int n, float inv_count, float* __restrict__ mean) {
+__global__ __launch_bounds__(256) void k_warp_geometry(const float* __restrict__ disp, const float* __restrict__ T_rel,
+                                                       const float* __restrict__ K, const float* __restrict__ K_inv,
+                                                       const float* __restrict__ baseline, int H, int W,
+                                                       float* __restrict__ cur_disp, float* __restrict__ valid,
+                                                       float* __restrict__ flow, float* __restrict__ partial) {
+    warp_geometry_body<false>(disp, T_rel, K, K_inv, baseline, nullptr, H, W, cur_disp, valid, flow, partial);
+}
+
+__global__ __launch_bounds__(256) void k_warp_geometry_mixed(const float* __restrict__ disp, const float* __restrict__ T_rel,
+                                                             const float* __restrict__ K, const float* __restrict__ K_inv,
+                                                             const float* __restrict__ baseline, const unsigned char* __restrict__ start,
+                                                             int H, int W, float* __restrict__ cur_disp, float* __restrict__ valid,
+                                                             float* __restrict__ flow, float* __restrict__ partial) {
+    warp_geometry_body<true>(disp, T_rel, K, K_inv, baseline, start, H, W, cur_disp, valid, flow, partial);
+}
+
+// fixed-order reduction of the partial sums (the total is valid in thread 0)
+__device__ __forceinline__ float partial_total(const float* __restrict__ partial, int n) {
     __shared__ float red[4];
     float s = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) s += partial[i];
     s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) *mean = ((red[0] + red[1]) + (red[2] + red[3])) * inv_count;
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// -> mean over ALL pixels of the batch (geo_utils.py:193)
+__global__ __launch_bounds__(256) void k_mean(const float* __restrict__ partial, int n, float inv_count, float* __restrict__ mean) {
+    const float t = partial_total(partial, n);
+    if (threadIdx.x == 0) *mean = t * inv_count;
+}
+
+// -> mean over the pixels of the temporal elements (start[b] == 0) only: the reference's warp() on that sub-batch.  The reciprocal is
+// formed as the host forms k_mean's; without a temporal element the mean is 0 (no 0/0; nothing reads it then).
+__global__ __launch_bounds__(256) void k_mean_mixed(const float* __restrict__ partial, int n, const unsigned char* __restrict__ start, int B,
+                                                    long long HW, float* __restrict__ mean) {
+    const float t = partial_total(partial, n);
+    if (threadIdx.x == 0) {
+        long long count = 0;
+        for (int b = 0; b < B; ++b) count += start[b] ? 0 : HW;
+        *mean = count > 0 ? t * (1.0f / (float)count) : 0.f;
+    }
 }
 
 __global__ __launch_bounds__(256) void k_metric(const float* __restrict__ cur_disp, const float* __restrict__ mean, int n,
@@ -149,10 +197,38 @@ __global__ __launch_bounds__(256) void k_zero_fill(float4* __restrict__ p, size_
 // normalise (softsplat.py:257-270, 'clipeps'), split, and the temporal cost (tc_stereo.py:139-140)
 // One block = 64 consecutive pixels x 4 channel quarters (one wave each: coalesced rows of 64 floats per channel); the
 // three sums of the cosine are combined across the quarters through LDS in a fixed order (deterministic).
-__global__ __launch_bounds__(256) void k_warp_finish(const float* __restrict__ acc, const float* __restrict__ cur_fmap,
-                                                     int C, int HW, float* __restrict__ out_disp, float* __restrict__ out_fmap,
-                                                     float* __restrict__ out_mask, float* __restrict__ out_cost) {
+// A start element of a mixed batch (start[b] != 0) reads neither the accumulator nor cur_fmap: its disparity, mask and cost are the
+// first-frame prior (tcs_corr_build's sparse_*), its warped features 0.  Block-uniform: the whole block returns before the barrier.
+template <bool MIXED>
+__device__ __forceinline__ bool finish_start(const unsigned char* __restrict__ start, const float* __restrict__ prior_disp,
+                                             const float* __restrict__ prior_cost, const float* __restrict__ prior_mask, int C, int HW,
+                                             float* __restrict__ out_disp, float* __restrict__ out_fmap, float* __restrict__ out_mask,
+                                             float* __restrict__ out_cost) {
+    const int b = blockIdx.y, lane = threadIdx.x & 63, q = threadIdx.x >> 6;
+    if (!MIXED || !start[b]) return false;
+    const int p = blockIdx.x * 64 + lane;
+    if (p >= HW) return true;
+    const size_t i = (size_t)b * HW + p;
+    if (q == 0) {
+        out_disp[i] = prior_disp[i];
+        out_mask[i] = prior_mask[i];
+        if (out_cost) out_cost[i] = prior_cost[i];
+    }
+    if (out_fmap) {
+        const int cq = (C + 3) / 4, c_lo = q * cq, c_hi = min(C, c_lo + cq);
+        for (int c = c_lo; c < c_hi; ++c) out_fmap[((size_t)b * C + c) * HW + p] = 0.f;
+    }
+    return true;
+}
+
+template <bool MIXED>
+__device__ __forceinline__ void warp_finish_body(const float* __restrict__ acc, const float* __restrict__ cur_fmap,
+                                                 const unsigned char* __restrict__ start, const float* __restrict__ prior_disp,
+                                                 const float* __restrict__ prior_cost, const float* __restrict__ prior_mask,
+                                                 int C, int HW, float* __restrict__ out_disp, float* __restrict__ out_fmap,
+                                                 float* __restrict__ out_mask, float* __restrict__ out_cost) {
     __shared__ float s_part[3][4][64];
+    if (finish_start<MIXED>(start, prior_disp, prior_cost, prior_mask, C, HW, out_disp, out_fmap, out_mask, out_cost)) return;
     const int b = blockIdx.y, lane = threadIdx.x & 63, q = threadIdx.x >> 6;
     const int p_raw = blockIdx.x * 64 + lane;
     const bool active = p_raw < HW;
@@ -186,6 +262,20 @@ __global__ __launch_bounds__(256) void k_warp_finish(const float* __restrict__ a
         for (int k = 0; k < 3; ++k) t[k] = ((s_part[k][0][lane] + s_part[k][1][lane]) + s_part[k][2][lane]) + s_part[k][3][lane];
         out_cost[(size_t)b * HW + p] = t[0] / (fmaxf(sqrtf(t[1]), 1e-12f) * fmaxf(sqrtf(t[2]), 1e-12f)) * mask;
     }
+}
+
+__global__ __launch_bounds__(256) void k_warp_finish(const float* __restrict__ acc, const float* __restrict__ cur_fmap,
+                                                     int C, int HW, float* __restrict__ out_disp, float* __restrict__ out_fmap,
+                                                     float* __restrict__ out_mask, float* __restrict__ out_cost) {
+    warp_finish_body<false>(acc, cur_fmap, nullptr, nullptr, nullptr, nullptr, C, HW, out_disp, out_fmap, out_mask, out_cost);
+}
+
+__global__ __launch_bounds__(256) void k_warp_finish_mixed(const float* __restrict__ acc, const float* __restrict__ cur_fmap,
+                                                           const unsigned char* __restrict__ start, const float* __restrict__ prior_disp,
+                                                           const float* __restrict__ prior_cost, const float* __restrict__ prior_mask,
+                                                           int C, int HW, float* __restrict__ out_disp, float* __restrict__ out_fmap,
+                                                           float* __restrict__ out_mask, float* __restrict__ out_cost) {
+    warp_finish_body<true>(acc, cur_fmap, start, prior_disp, prior_cost, prior_mask, C, HW, out_disp, out_fmap, out_mask, out_cost);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -353,13 +443,17 @@ __global__ __launch_bounds__(256) void k_ord_sum_gather(const int* __restrict__ 
 
 // MODE 1: the ordered sums of warp() + k_warp_finish's normalisation, split and cosine cost, in k_warp_finish's layout and arithmetic.
 // Channel order of the sums as k_splat's accumulator: [0,C) prev_fmap * s, C the new disparity * s, C+1 the normaliser s.
-__global__ __launch_bounds__(256) void k_ord_warp_gather(const int* __restrict__ start, const int* __restrict__ count,
-                                                         const int2* __restrict__ sorted, const float* __restrict__ prev_fmap,
-                                                         const float* __restrict__ cur_disp, const float* __restrict__ scale,
-                                                         const float* __restrict__ cur_fmap, int C, int HW, float* __restrict__ out_disp,
-                                                         float* __restrict__ out_fmap, float* __restrict__ out_mask, float* __restrict__ out_cost) {
+template <bool MIXED>
+__device__ __forceinline__ void ord_warp_gather_body(const int* __restrict__ start, const int* __restrict__ count,
+                                                     const int2* __restrict__ sorted, const float* __restrict__ prev_fmap,
+                                                     const float* __restrict__ cur_disp, const float* __restrict__ scale,
+                                                     const float* __restrict__ cur_fmap, const unsigned char* __restrict__ seq_start,
+                                                     const float* __restrict__ prior_disp, const float* __restrict__ prior_cost,
+                                                     const float* __restrict__ prior_mask, int C, int HW, float* __restrict__ out_disp,
+                                                     float* __restrict__ out_fmap, float* __restrict__ out_mask, float* __restrict__ out_cost) {
 #pragma clang fp contract(off)
     __shared__ float s_part[3][4][64];
+    if (finish_start<MIXED>(seq_start, prior_disp, prior_cost, prior_mask, C, HW, out_disp, out_fmap, out_mask, out_cost)) return;
     const int b = blockIdx.y, lane = threadIdx.x & 63, q = threadIdx.x >> 6;
     const int p_raw = blockIdx.x * 64 + lane;
     const bool active = p_raw < HW;
@@ -405,6 +499,27 @@ __global__ __launch_bounds__(256) void k_ord_warp_gather(const int* __restrict__
     }
 }
 
+__global__ __launch_bounds__(256) void k_ord_warp_gather(const int* __restrict__ start, const int* __restrict__ count,
+                                                         const int2* __restrict__ sorted, const float* __restrict__ prev_fmap,
+                                                         const float* __restrict__ cur_disp, const float* __restrict__ scale,
+                                                         const float* __restrict__ cur_fmap, int C, int HW, float* __restrict__ out_disp,
+                                                         float* __restrict__ out_fmap, float* __restrict__ out_mask, float* __restrict__ out_cost) {
+    ord_warp_gather_body<false>(start, count, sorted, prev_fmap, cur_disp, scale, cur_fmap, nullptr, nullptr, nullptr, nullptr, C, HW,
+                                out_disp, out_fmap, out_mask, out_cost);
+}
+
+__global__ __launch_bounds__(256) void k_ord_warp_gather_mixed(const int* __restrict__ start, const int* __restrict__ count,
+                                                               const int2* __restrict__ sorted, const float* __restrict__ prev_fmap,
+                                                               const float* __restrict__ cur_disp, const float* __restrict__ scale,
+                                                               const float* __restrict__ cur_fmap, const unsigned char* __restrict__ seq_start,
+                                                               const float* __restrict__ prior_disp, const float* __restrict__ prior_cost,
+                                                               const float* __restrict__ prior_mask, int C, int HW,
+                                                               float* __restrict__ out_disp, float* __restrict__ out_fmap,
+                                                               float* __restrict__ out_mask, float* __restrict__ out_cost) {
+    ord_warp_gather_body<true>(start, count, sorted, prev_fmap, cur_disp, scale, cur_fmap, seq_start, prior_disp, prior_cost, prior_mask,
+                               C, HW, out_disp, out_fmap, out_mask, out_cost);
+}
+
 // ------------------------------------------------------------------------------------------------
 // backward grid (geo_utils.py:201-236)
 // ------------------------------------------------------------------------------------------------
@@ -424,12 +539,19 @@ __global__ __launch_bounds__(256) void k_backward_grid(const float* __restrict__
 }
 
 // bilinear_sampler (utils.py:82-97): zeros padding, align_corners=True, pixel coordinates
-__global__ __launch_bounds__(256) void k_bilinear_sample(const float* __restrict__ img, const float* __restrict__ grid,
-                                                         int C, int Hi, int Wi, int HWo, int ch_per_group,
-                                                         float* __restrict__ out) {
+// MIXED: a start element (start[b] != 0) gets +0.0 everywhere and reads neither img nor grid (the first frame's zero hidden states)
+template <bool MIXED>
+__device__ __forceinline__ void bilinear_sample_body(const float* __restrict__ img, const float* __restrict__ grid,
+                                                     const unsigned char* __restrict__ start, int C, int Hi, int Wi, int HWo,
+                                                     int ch_per_group, float* __restrict__ out) {
     const int b = blockIdx.y;
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= HWo) return;
+    if (MIXED && start[b]) {
+        const int c_lo = blockIdx.z * ch_per_group, c_hi = min(C, c_lo + ch_per_group);
+        for (int c = c_lo; c < c_hi; ++c) out[((size_t)b * C + c) * HWo + p] = 0.f;
+        return;
+    }
     float gx = grid[((size_t)b * 2 + 0) * HWo + p], gy = grid[((size_t)b * 2 + 1) * HWo + p];
     const bool fin = isfinite(gx) && isfinite(gy);
     gx = fminf(fmaxf(fin ? gx : -8.f, -8.f), (float)Wi + 8.f);
@@ -452,6 +574,18 @@ __global__ __launch_bounds__(256) void k_bilinear_sample(const float* __restrict
         const float bot = (1.f - ax) * v10 + ax * v11;
         out[((size_t)b * C + c) * HWo + p] = (1.f - ay) * top + ay * bot;
     }
+}
+
+__global__ __launch_bounds__(256) void k_bilinear_sample(const float* __restrict__ img, const float* __restrict__ grid,
+                                                         int C, int Hi, int Wi, int HWo, int ch_per_group,
+                                                         float* __restrict__ out) {
+    bilinear_sample_body<false>(img, grid, nullptr, C, Hi, Wi, HWo, ch_per_group, out);
+}
+
+__global__ __launch_bounds__(256) void k_bilinear_sample_mixed(const float* __restrict__ img, const float* __restrict__ grid,
+                                                               const unsigned char* __restrict__ start, int C, int Hi, int Wi, int HWo,
+                                                               int ch_per_group, float* __restrict__ out) {
+    bilinear_sample_body<true>(img, grid, start, C, Hi, Wi, HWo, ch_per_group, out);
 }
 
 // bilinear resize, align_corners=True (F.interpolate), times `scale`
@@ -506,15 +640,21 @@ __device__ void matmul4(const float* a, const float* b, float* o) {
         }
 }
 
-__global__ void k_pose_prepare(const float* __restrict__ K, const float* __restrict__ T, const float* __restrict__ Tp, float scale,
-                               int B, float* __restrict__ Ks, float* __restrict__ Ksi, float* __restrict__ Trel,
-                               float* __restrict__ Tback) {
+// MIXED: a start element (start[b] != 0) gets identity T_rel / T_back without reading its T or T_prev; its K is scaled as usual
+template <bool MIXED>
+__device__ __forceinline__ void pose_prepare_body(const float* __restrict__ K, const float* __restrict__ T, const float* __restrict__ Tp,
+                                                  const unsigned char* __restrict__ start, float scale, int B, float* __restrict__ Ks,
+                                                  float* __restrict__ Ksi, float* __restrict__ Trel, float* __restrict__ Tback) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     float ks[9], inv3[9];
     for (int i = 0; i < 9; ++i) ks[i] = K[b * 9 + i] * (i < 6 ? scale : 1.f);     // rows 0,1 scaled (tc_stereo.py:122)
     invert_small<3>(ks, inv3);
     for (int i = 0; i < 9; ++i) { Ks[b * 9 + i] = ks[i]; Ksi[b * 9 + i] = inv3[i]; }
+    if (MIXED && start[b]) {
+        for (int i = 0; i < 16; ++i) Trel[b * 16 + i] = Tback[b * 16 + i] = (i % 5 == 0) ? 1.f : 0.f;
+        return;
+    }
     if (T && Tp) {
         float inv4[16], o[16];
         invert_small<4>(Tp + b * 16, inv4);
@@ -524,6 +664,18 @@ __global__ void k_pose_prepare(const float* __restrict__ K, const float* __restr
         matmul4(Tp + b * 16, inv4, o);                                            // tc_stereo.py:159
         for (int i = 0; i < 16; ++i) Tback[b * 16 + i] = o[i];
     }
+}
+
+__global__ void k_pose_prepare(const float* __restrict__ K, const float* __restrict__ T, const float* __restrict__ Tp, float scale,
+                               int B, float* __restrict__ Ks, float* __restrict__ Ksi, float* __restrict__ Trel,
+                               float* __restrict__ Tback) {
+    pose_prepare_body<false>(K, T, Tp, nullptr, scale, B, Ks, Ksi, Trel, Tback);
+}
+
+__global__ void k_pose_prepare_mixed(const float* __restrict__ K, const float* __restrict__ T, const float* __restrict__ Tp,
+                                     const unsigned char* __restrict__ start, float scale, int B, float* __restrict__ Ks,
+                                     float* __restrict__ Ksi, float* __restrict__ Trel, float* __restrict__ Tback) {
+    pose_prepare_body<true>(K, T, Tp, start, scale, B, Ks, Ksi, Trel, Tback);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -614,9 +766,16 @@ size_t tcs_warp_workspace_bytes(int B, int C, int H, int W) {
            al256((size_t)B * (C + 2) * HW * 4);
 }
 
+// `start` (device, [B]): the mixed geometry (start elements skipped, the mean over the temporal elements' pixels); nullptr: today's
 static int geometry(const float* prev_disp, const float* T_rel, const float* K, const float* K_inv, const float* baseline,
-                    int B, int H, int W, const WarpWs& w, hipStream_t s) {
+                    int B, int H, int W, const WarpWs& w, hipStream_t s, const unsigned char* start = nullptr) {
     const int nb = tcs_cdiv((long long)H * W, 256);
+    if (start) {
+        hipLaunchKernelGGL(k_warp_geometry_mixed, dim3(nb, B), dim3(256), 0, s, prev_disp, T_rel, K, K_inv, baseline, start, H, W,
+                           w.cur_disp, w.valid, w.flow, w.partial);
+        hipLaunchKernelGGL(k_mean_mixed, dim3(1), dim3(256), 0, s, w.partial, nb * B, start, B, (long long)H * W, w.mean);
+        return tcs_launch_status();
+    }
     hipLaunchKernelGGL(k_warp_geometry, dim3(nb, B), dim3(256), 0, s, prev_disp, T_rel, K, K_inv, baseline, H, W,
                        w.cur_disp, w.valid, w.flow, w.partial);
     hipLaunchKernelGGL(k_mean, dim3(1), dim3(256), 0, s, w.partial, nb * B, 1.0f / (float)((long long)B * H * W), w.mean);
@@ -664,6 +823,34 @@ int tcs_warp_forward(const float* prev_disp, const float* prev_fmap, const float
     return tcs_launch_status();
 }
 
+int tcs_warp_forward_mixed(const float* prev_disp, const float* prev_fmap, const float* T_rel, const float* K,
+                           const float* K_inv, const float* baseline, const unsigned char* start, const float* prior_disp,
+                           const float* prior_cost, const float* prior_mask, int B, int C, int H, int W,
+                           float* out_disp, float* out_fmap, float* out_mask, const float* cur_fmap, float* out_cost,
+                           void* workspace, tcs_stream_t stream) {
+    if (!prev_disp || !prev_fmap || !T_rel || !K || !K_inv || !baseline || !out_disp || !out_mask || !workspace)
+        return TCS_EINVAL;
+    if (!start || !prior_disp || !prior_cost || !prior_mask) return TCS_EINVAL;
+    if ((cur_fmap == nullptr) != (out_cost == nullptr)) return TCS_EINVAL;
+    if (B <= 0 || B > 65535 || C <= 0 || H <= 0 || W <= 0) return TCS_EINVAL;
+    hipStream_t s = tcs_stream(stream);
+    WarpWs w = carve(workspace, B, C, H, W);
+    int rc = geometry(prev_disp, T_rel, K, K_inv, baseline, B, H, W, w, s, start);
+    if (rc) return rc;
+    {
+        const size_t n4 = (w.acc_bytes + 15) / 16;
+        hipLaunchKernelGGL(k_zero_fill, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<float4*>(w.acc), n4);
+    }
+    const int nb = tcs_cdiv((long long)H * W, 256);
+    const int cpg = 16, groups = tcs_cdiv(C + 2, cpg);
+    // (start elements have valid = 0 everywhere: k_splat skips every one of their pixels)
+    hipLaunchKernelGGL(k_splat<1>, dim3(nb, B, groups), dim3(256), 0, s, prev_fmap, w.flow, w.cur_disp, w.valid, w.mean,
+                       C, H, W, cpg, w.acc);
+    hipLaunchKernelGGL(k_warp_finish_mixed, dim3(tcs_cdiv((long long)H * W, 64), B), dim3(256), 0, s, w.acc, cur_fmap, start, prior_disp,
+                       prior_cost, prior_mask, C, H * W, out_disp, out_fmap, out_mask, out_cost);
+    return tcs_launch_status();
+}
+
 int tcs_softsplat_sum(const float* in, const float* flow, int B, int C, int H, int W, float* out, tcs_stream_t stream) {
     if (!in || !flow || !out || B <= 0 || B > 65535 || C <= 0 || H <= 0 || W <= 0) return TCS_EINVAL;
     const int nb = tcs_cdiv((long long)H * W, 256);
@@ -689,6 +876,28 @@ int tcs_warp_forward_ordered(const float* prev_disp, const float* prev_fmap, con
     ord_index<1>(w.flow, w.cur_disp, w.valid, w.mean, B, H, W, o, s);
     hipLaunchKernelGGL(k_ord_warp_gather, dim3(tcs_cdiv((long long)H * W, 64), B), dim3(256), 0, s, o.start, o.count, o.sorted, prev_fmap,
                        w.cur_disp, o.scale, cur_fmap, C, H * W, out_disp, out_fmap, out_mask, out_cost);
+    return tcs_launch_status();
+}
+
+int tcs_warp_forward_ordered_mixed(const float* prev_disp, const float* prev_fmap, const float* T_rel, const float* K,
+                                   const float* K_inv, const float* baseline, const unsigned char* start, const float* prior_disp,
+                                   const float* prior_cost, const float* prior_mask, int B, int C, int H, int W,
+                                   float* out_disp, float* out_fmap, float* out_mask, const float* cur_fmap, float* out_cost,
+                                   void* workspace, tcs_stream_t stream) {
+    if (!prev_disp || !prev_fmap || !T_rel || !K || !K_inv || !baseline || !out_disp || !out_mask || !workspace)
+        return TCS_EINVAL;
+    if (!start || !prior_disp || !prior_cost || !prior_mask) return TCS_EINVAL;
+    if ((cur_fmap == nullptr) != (out_cost == nullptr)) return TCS_EINVAL;
+    if (B <= 0 || B > 65535 || C <= 0 || H <= 0 || W <= 0 || !ord_dims_ok(B, H, W)) return TCS_EINVAL;
+    hipStream_t s = tcs_stream(stream);
+    const WarpWs w = carve(workspace, B, C, H, W);
+    int rc = geometry(prev_disp, T_rel, K, K_inv, baseline, B, H, W, w, s, start);
+    if (rc) return rc;
+    const OrdWs o = carve_ord(w.acc, B, (size_t)H * W, true);
+    ord_index<1>(w.flow, w.cur_disp, w.valid, w.mean, B, H, W, o, s);         // (valid = 0: no index entries for start elements)
+    hipLaunchKernelGGL(k_ord_warp_gather_mixed, dim3(tcs_cdiv((long long)H * W, 64), B), dim3(256), 0, s, o.start, o.count, o.sorted,
+                       prev_fmap, w.cur_disp, o.scale, cur_fmap, start, prior_disp, prior_cost, prior_mask, C, H * W, out_disp, out_fmap,
+                       out_mask, out_cost);
     return tcs_launch_status();
 }
 
@@ -721,6 +930,15 @@ int tcs_bilinear_sample(const float* img, const float* grid, int B, int C, int H
     return tcs_launch_status();
 }
 
+int tcs_bilinear_sample_mixed(const float* img, const float* grid, const unsigned char* start, int B, int C, int Hi, int Wi, int Ho,
+                              int Wo, float* out, tcs_stream_t stream) {
+    if (!img || !grid || !start || !out || B <= 0 || B > 65535 || C <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0) return TCS_EINVAL;
+    const int cpg = 16;
+    hipLaunchKernelGGL(k_bilinear_sample_mixed, dim3(tcs_cdiv((long long)Ho * Wo, 256), B, tcs_cdiv(C, cpg)), dim3(256), 0,
+                       tcs_stream(stream), img, grid, start, C, Hi, Wi, Ho * Wo, cpg, out);
+    return tcs_launch_status();
+}
+
 int tcs_grid_halve(const float* grid, int B, int H, int W, float* out, tcs_stream_t stream) {
     if (!grid || !out || B <= 0 || H < 2 || W < 2) return TCS_EINVAL;
     const int Ho = H / 2, Wo = W / 2;
@@ -735,6 +953,14 @@ int tcs_pose_prepare(const float* K, const float* T, const float* T_prev, float 
     if ((T == nullptr) != (T_prev == nullptr)) return TCS_EINVAL;
     if (T && (!T_rel || !T_back)) return TCS_EINVAL;
     hipLaunchKernelGGL(k_pose_prepare, dim3(tcs_cdiv(B, 64)), dim3(64), 0, tcs_stream(stream), K, T, T_prev, scale, B,
+                       K_scaled, K_scaled_inv, T_rel, T_back);
+    return tcs_launch_status();
+}
+
+int tcs_pose_prepare_mixed(const float* K, const float* T, const float* T_prev, const unsigned char* start, float scale, int B,
+                           float* K_scaled, float* K_scaled_inv, float* T_rel, float* T_back, tcs_stream_t stream) {
+    if (!K || !T || !T_prev || !start || !K_scaled || !K_scaled_inv || !T_rel || !T_back || B <= 0) return TCS_EINVAL;
+    hipLaunchKernelGGL(k_pose_prepare_mixed, dim3(tcs_cdiv(B, 64)), dim3(64), 0, tcs_stream(stream), K, T, T_prev, start, scale, B,
                        K_scaled, K_scaled_inv, T_rel, T_back);
     return tcs_launch_status();
 }

@@ -35,16 +35,24 @@ _CAPTURING = 0          # > 0 while any FrameGraphs capture is recording (FrameG
 
 
 def _flatten(temporal):
+    """A mixed batch's temporal tuple has an 8th entry, the uint8 [B] sequence-start mask: one more static input of REFINE."""
     if temporal is None:
         return []
-    K, T, Tp, base, last_disp, nets, fmap1 = temporal
-    return [K, T, Tp, base, last_disp, *nets, fmap1]
+    K, T, Tp, base, last_disp, nets, fmap1 = temporal[:7]
+    return [K, T, Tp, base, last_disp, *nets, fmap1, *temporal[7:]]
 
 
 def _unflatten(flat):
     if not flat:
         return None
+    if flat[-1].dtype == torch.uint8:
+        return _unflatten(flat[:-1]) + (flat[-1],)
     return (flat[0], flat[1], flat[2], flat[3], flat[4], list(flat[5:-1]), flat[-1])
+
+
+def _wants_argmax(temporal):
+    """A first frame and every frame of a mixed batch consume an EXTRACT made with the arg-max prior (the `first=True` extract key)."""
+    return temporal is None or len(temporal) == 8
 
 
 def _tensors(obj, seen=None):
@@ -259,6 +267,8 @@ class FrameGraphs:
 
     def prefetch(self, image1, image2, first: bool = False, use_graph: bool = True, inputs_ready: bool = False) -> int:
         """Launch the EXTRACT stage of a coming frame; the next `__call__` with the same image tensor objects (unmodified) uses it.
+        `first=True` for a frame that will be called with params=None OR as a mixed batch (params["new_sequence"] present, whatever
+        its values): both consume the extract made with the arg-max prior.  A mixed frame does not pick up a `first=False` prefetch.
         Call it right after the `__call__` it is to overlap with, with `inputs_ready=True` when the images were on the device before
         that call (see `_launch_extract`).  Returns the slot."""
         self._check_epoch()
@@ -282,7 +292,7 @@ class FrameGraphs:
             if self.ex.get(ex_key) is None:
                 return None                          # the extract stage runs eagerly: so does this one
             torch.cuda.synchronize()
-            static_in = [t.detach().float().clone() for t in flat]
+            static_in = [t.detach().clone() if t.dtype == torch.uint8 else t.detach().float().clone() for t in flat]
             entries = []
             for si in (0, 1):
                 feats = self.ex[ex_key][si].static_out
@@ -318,7 +328,7 @@ class FrameGraphs:
     def __call__(self, image1, image2, iters, temporal, use_graph: bool = True):
         self._check_epoch()
         flat = _flatten(temporal)
-        first = temporal is None
+        first = _wants_argmax(temporal)
         token = self._token(image1, image2, first, use_graph)
         entries = None
         if use_graph:

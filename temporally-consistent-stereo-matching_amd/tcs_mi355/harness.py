@@ -135,6 +135,132 @@ def run_sequence(forward: Callable, seq, iters: int, device, temporal: bool = Tr
     return stats
 
 
+def _padded_shape(seq, divis_by: int):
+    f = seq.frames[0]
+    p = InputPadder(np.shape(f.image1), divis_by=divis_by)
+    return (int(np.shape(f.image1)[0]), p.ht + p.top + p.bottom, p.wd + p.left + p.right)
+
+
+@torch.no_grad()
+def run_sequences(forward: Callable, seqs, iters: int, device, batch: int, temporal: bool = True, divis_by: int = 32,
+                  collect: Optional[list] = None, prefetch: bool = False) -> List[SequenceStats]:
+    """Continuous batching: the sequences `seqs` through `forward` over `batch` slots of one batch dimension, each slot running one
+    sequence at a time.  A slot whose sequence has ended takes the next one, and that element is called with
+    `params["new_sequence"][slot] = True` (TCStereo.forward's mixed batch: a first frame for it, a temporal frame for the others).
+    The first call is `params=None`; a call in which no slot starts a sequence carries no `new_sequence` key (the temporal path).
+    K, T and baseline are stacked per slot and the state is threaded per slot as `run_sequence` threads it.  The batch stays
+    `batch` wide: a slot with nothing left to run holds a padding element (zero images, marked as a sequence start) whose outputs
+    are discarded and never counted, so no new shape is captured.  Sequences are taken longest first (a shorter padded tail);
+    the results do not depend on the input order.
+
+    Returns one `SequenceStats` per sequence, in input order, with `run_sequence`'s per-frame metrics; `collect`, if given,
+    receives one list per sequence (input order) of its unpadded predictions.  `domain_flags` is RUN-level: the device-side flags
+    are read once, after the last call, and every sequence of the run reports that value.  `temporal=False` calls every frame with
+    params=None.  Sequences whose padded shapes differ raise ValueError.  `prefetch=True` needs `forward` to be a TCStereo: each
+    call is followed by `forward.prefetch` of the next call's images (`first=True` when any slot starts on that call)."""
+    seqs = list(seqs)
+    if batch < 1:
+        raise ValueError("batch must be >= 1")
+    if prefetch:
+        from core.tc_stereo import TCStereo
+        if not isinstance(forward, TCStereo):
+            raise ValueError("run_sequences(prefetch=True) needs a TCStereo as `forward` (it calls forward.prefetch)")
+    stats = [SequenceStats() for _ in seqs]
+    preds: List[list] = [[] for _ in seqs]
+    if seqs:
+        shapes = {_padded_shape(q, divis_by) for q in seqs}
+        if len(shapes) > 1:
+            raise ValueError(f"run_sequences needs one padded shape for all sequences, got {sorted(shapes)}")
+    queue = sorted(range(len(seqs)), key=lambda i: (-len(seqs[i].frames), i))     # longest first; ties in input order
+    queue = [i for i in queue if seqs[i].frames]
+    slot_seq: List[Optional[int]] = [None] * batch      # the sequence a slot runs, None = idle (padding)
+    slot_pos = [0] * batch                              # its next frame
+    pad_like = None                                     # (a real slot's inputs: shapes and a finite K / T for padding elements)
+
+    def assign():
+        """Fill idle slots from the queue; -> the per-slot sequence-start flags of the coming call."""
+        starts = []
+        for b in range(batch):
+            if slot_seq[b] is not None and slot_pos[b] >= len(seqs[slot_seq[b]].frames):
+                slot_seq[b] = None
+            if slot_seq[b] is None and queue:
+                slot_seq[b], slot_pos[b] = queue.pop(0), 0
+            starts.append(slot_seq[b] is None or slot_pos[b] == 0)
+        return starts
+
+    def inputs():
+        """The stacked inputs of the coming call: padded images, shifted K, T, baseline, and the padders / ground truth per slot."""
+        nonlocal pad_like
+        per = []
+        for b in range(batch):
+            i = slot_seq[b]
+            if i is None:
+                per.append(None)
+                continue
+            q = seqs[i]
+            fr = q.frames[slot_pos[b]]
+            im1 = torch.as_tensor(fr.image1, device=device)[None]
+            im2 = torch.as_tensor(fr.image2, device=device)[None]
+            padder = InputPadder(im1.shape, divis_by=divis_by)
+            K_raw = torch.as_tensor(q.K, dtype=torch.float32, device=device)[None]
+            (im1, im2), K = padder.pad(im1, im2, K=K_raw)
+            T = torch.as_tensor(fr.T, device=device)[None]
+            base = torch.tensor([q.baseline], dtype=torch.float32, device=device)
+            per.append((im1, im2, K, T, base, padder, torch.as_tensor(fr.disp_gt, device=device)[None]))
+            if pad_like is None:
+                pad_like = per[-1]
+        rows = [p if p is not None else (torch.zeros_like(pad_like[0]), torch.zeros_like(pad_like[1]), pad_like[2], pad_like[3],
+                                         pad_like[4], None, None) for p in per]
+        cat = lambda k: torch.cat([r[k] for r in rows], 0)
+        return cat(0), cat(1), cat(2), cat(3), cat(4), rows
+
+    starts = assign()
+    nxt = inputs() if any(s is not None for s in slot_seq) else None
+    first_call = True
+    prev_T = out = None
+    while nxt is not None:
+        im1, im2, K, T, base, rows = nxt
+        if first_call or not temporal:
+            params = None
+        else:
+            params = {"K": K, "T": T, "previous_T": prev_T, "baseline": base, "last_disp": out["flow_q"],
+                      "last_net_list": out["net_list"], "fmap1": out["fmap1"]}
+            if any(starts):
+                params["new_sequence"] = torch.tensor(starts, dtype=torch.bool, device=device)
+        running = list(slot_seq)
+        out = forward(im1, im2, iters=iters, test_mode=True, params=params)
+        first_call = False
+        # previous_T of a start element is never read: its current T keeps the stacked tensor finite
+        prev_T = T
+        for b in range(batch):
+            slot_pos[b] += int(running[b] is not None)
+        starts = assign()
+        nxt = inputs() if any(s is not None for s in slot_seq) else None
+        if prefetch and nxt is not None:
+            forward.prefetch(nxt[0], nxt[1], first=(not temporal) or any(starts))
+        for b, i in enumerate(running):
+            if i is None:
+                continue                                          # padding: discarded
+            padder, gt = rows[b][5], rows[b][6]
+            disp_pr = padder.unpad(-out["flow"][b:b + 1])
+            preds[i].append(disp_pr)
+            fs = frame_metrics(disp_pr, gt)
+            if fs is not None:
+                stats[i].frames.append(fs)
+    if torch.device(device).type == "cuda":
+        from . import s16
+        flags = s16.take_flags()
+        for st in stats:
+            st.domain_flags = flags
+        if flags:
+            import warnings
+            warnings.warn(f"activations left the fp16-split domain during this run (flags {flags:#x}: "
+                          f"bit 0 = clamped at 65504, bit 1 = NaN/Inf)")
+    if collect is not None:
+        collect.extend(preds)
+    return stats
+
+
 # ---------------------------------------------------------------------------------------------------
 # real data, when the box has it (BASELINE configs[2]): TartanAir trajectory folder + reference checkpoint
 # ---------------------------------------------------------------------------------------------------

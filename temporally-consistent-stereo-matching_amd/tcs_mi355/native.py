@@ -76,6 +76,7 @@ SIGNATURES = {
     "tcs_corr_lookup": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp]),
     "tcs_corr_lookup_blocks": (c_int, [c_int, c_int, c_int]),
     "tcs_pose_prepare": (c_int, [c_fp, c_fp, c_fp, c_f, c_int, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "tcs_pose_prepare_mixed": (c_int, [c_fp, c_fp, c_fp, c_fp, c_f, c_int, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "tcs_warp_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
     "tcs_warp_forward": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp,
                                  c_fp, c_fp]),
@@ -84,10 +85,15 @@ SIGNATURES = {
     "tcs_warp_ordered_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
     "tcs_warp_forward_ordered": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp,
                                          c_fp, c_fp]),
+    "tcs_warp_forward_mixed": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp,
+                                       c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "tcs_warp_forward_ordered_mixed": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int,
+                                               c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "tcs_softsplat_ordered_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
     "tcs_softsplat_sum_ordered": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp]),
     "tcs_backward_grid": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp]),
     "tcs_bilinear_sample": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp]),
+    "tcs_bilinear_sample_mixed": (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp]),
     "tcs_grid_halve": (c_int, [c_fp, c_int, c_int, c_int, c_fp, c_fp]),
     "tcs_flow_step": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp]),
     "tcs_flow_step_grads": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_f, c_fp, c_fp, c_fp, c_fp]),

@@ -117,8 +117,21 @@ class LookupProbe:
 LOOKUP_PROBE: Optional[LookupProbe] = None
 
 
-def pose_prepare(K, T=None, T_prev=None, scale: float = 0.25):
-    """-> (K_scaled, K_scaled_inv, T_rel, T_back); the last two are None without poses (tcs_pose_prepare)."""
+def _start(start, B: int, device) -> torch.Tensor:
+    """A mixed batch's sequence-start mask as the kernels take it: uint8 [B] on the device of the data (bool is converted there)."""
+    if not torch.is_tensor(start) or start.ndim != 1 or int(start.shape[0]) != B or start.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f"start must be a bool / uint8 tensor of shape [{B}], got "
+                         f"{tuple(start.shape) if torch.is_tensor(start) else type(start).__name__}"
+                         f"{' ' + str(start.dtype) if torch.is_tensor(start) else ''}")
+    if start.device != device:
+        raise ValueError(f"start is on {start.device}, the data on {device}")
+    return start.to(torch.uint8).contiguous()
+
+
+def pose_prepare(K, T=None, T_prev=None, scale: float = 0.25, start=None):
+    """-> (K_scaled, K_scaled_inv, T_rel, T_back); the last two are None without poses (tcs_pose_prepare).
+    start: a mixed batch's sequence-start mask [B] (tcs_pose_prepare_mixed; needs the poses): identity T_rel / T_back for the start
+    elements, whose T / T_prev are not read.  None calls tcs_pose_prepare."""
     B = int(K.shape[0])
     K = K.reshape(B, 3, 3).float().contiguous()
     ks, ksi = torch.empty_like(K), torch.empty_like(K)
@@ -126,6 +139,14 @@ def pose_prepare(K, T=None, T_prev=None, scale: float = 0.25):
     if T is not None:
         T, T_prev = T.reshape(B, 4, 4).float().contiguous(), T_prev.reshape(B, 4, 4).float().contiguous()
         trel, tback = torch.empty_like(T), torch.empty_like(T)
+    if start is not None:
+        if T is None or T_prev is None:
+            raise ValueError("pose_prepare(start=...) needs T and T_prev")
+        start = _start(start, B, K.device)
+        nv.check(nv.lib().tcs_pose_prepare_mixed(nv.ptr(K, "K"), nv.ptr(T, "T"), nv.ptr(T_prev, "previous_T"),
+                                                 nv.ptr(start, "start", torch.uint8), float(scale), B, nv.ptr(ks), nv.ptr(ksi),
+                                                 nv.ptr(trel), nv.ptr(tback), nv.stream()), "tcs_pose_prepare_mixed")
+        return ks, ksi, trel, tback
     nv.check(nv.lib().tcs_pose_prepare(nv.ptr(K, "K"), nv.ptr(T, "T"), nv.ptr(T_prev, "previous_T"), float(scale), B,
                                        nv.ptr(ks), nv.ptr(ksi), nv.ptr(trel), nv.ptr(tback), nv.stream()), "tcs_pose_prepare")
     return ks, ksi, trel, tback
@@ -144,21 +165,43 @@ def _cam(T_rel, K, K_inv, baseline, B):
     return T_rel, K, K_inv, baseline
 
 
-def warp_forward(prev_disp, prev_fmap, T_rel, K, K_inv, baseline, cur_fmap=None, want_fmap=True, ordered=False):
+def warp_forward(prev_disp, prev_fmap, T_rel, K, K_inv, baseline, cur_fmap=None, want_fmap=True, ordered=False, start=None,
+                 prior=None):
     """-> (disp [B,1,H,W], fmap [B,C,H,W] or None, mask [B,1,H,W], cost [B,1,H,W] or None)
     ordered: the splat sums in a fixed order (tcs_warp_forward_ordered), so the outputs are bit-reproducible from run to run;
-    False is the float-atomic splat (tcs_warp_forward)."""
+    False is the float-atomic splat (tcs_warp_forward).
+    start, prior: a mixed batch (tcs_warp_forward[_ordered]_mixed).  start [B] marks the elements that begin a sequence, prior is
+    the first-frame prior (sparse_disp, cost, mask) [B,1,H,W] each (CorrBlock1D.argmax_disp).  A start element's disp / mask / cost
+    are its prior, its fmap 0, and none of its previous-frame inputs is read; the metric mean covers the other elements only.
+    None (both) calls today's entry points."""
     B, Cc, H, W = _dims4(prev_fmap, "prev_fmap")
     if tuple(prev_disp.shape) != (B, 1, H, W):
         raise ValueError("prev_disp must be [B,1,H,W] matching prev_fmap")
+    if (start is None) != (prior is None):
+        raise ValueError("warp_forward: start and prior go together")
     T_rel, K, K_inv, baseline = _cam(T_rel, K, K_inv, baseline, B)
     L = nv.lib()
-    ws_bytes, fn, name = ((L.tcs_warp_ordered_workspace_bytes, L.tcs_warp_forward_ordered, "tcs_warp_forward_ordered") if ordered else
-                          (L.tcs_warp_workspace_bytes, L.tcs_warp_forward, "tcs_warp_forward"))
-    ws = torch.empty(ws_bytes(B, Cc, H, W) // 4, dtype=torch.float32, device=prev_fmap.device)
     o_disp, o_mask = _new(prev_disp, B, 1, H, W), _new(prev_disp, B, 1, H, W)
     o_fmap = _new(prev_fmap, B, Cc, H, W) if want_fmap else None
     o_cost = _new(prev_disp, B, 1, H, W) if cur_fmap is not None else None
+    ws_bytes = L.tcs_warp_ordered_workspace_bytes if ordered else L.tcs_warp_workspace_bytes
+    ws = torch.empty(ws_bytes(B, Cc, H, W) // 4, dtype=torch.float32, device=prev_fmap.device)
+    if start is not None:
+        start = _start(start, B, prev_fmap.device)
+        pr = []
+        for t, nm in zip(prior, ("prior_disp", "prior_cost", "prior_mask")):
+            if tuple(t.shape) != (B, 1, H, W):
+                raise ValueError(f"{nm} must be [B,1,H,W] = {(B, 1, H, W)}, got {tuple(t.shape)}")
+            pr.append(t.float().contiguous())
+        fn, name = ((L.tcs_warp_forward_ordered_mixed, "tcs_warp_forward_ordered_mixed") if ordered else
+                    (L.tcs_warp_forward_mixed, "tcs_warp_forward_mixed"))
+        rc = fn(nv.ptr(prev_disp, "prev_disp"), nv.ptr(prev_fmap, "prev_fmap"), nv.ptr(T_rel), nv.ptr(K), nv.ptr(K_inv),
+                nv.ptr(baseline), nv.ptr(start, "start", torch.uint8), nv.ptr(pr[0], "prior_disp"), nv.ptr(pr[1], "prior_cost"),
+                nv.ptr(pr[2], "prior_mask"), B, Cc, H, W, nv.ptr(o_disp), nv.ptr(o_fmap), nv.ptr(o_mask),
+                nv.ptr(cur_fmap, "cur_fmap"), nv.ptr(o_cost), nv.ptr(ws), nv.stream())
+        nv.check(rc, name)
+        return o_disp, o_fmap, o_mask, o_cost
+    fn, name = ((L.tcs_warp_forward_ordered, "tcs_warp_forward_ordered") if ordered else (L.tcs_warp_forward, "tcs_warp_forward"))
     rc = fn(nv.ptr(prev_disp, "prev_disp"), nv.ptr(prev_fmap, "prev_fmap"), nv.ptr(T_rel), nv.ptr(K), nv.ptr(K_inv),
             nv.ptr(baseline), B, Cc, H, W, nv.ptr(o_disp), nv.ptr(o_fmap), nv.ptr(o_mask),
             nv.ptr(cur_fmap, "cur_fmap"), nv.ptr(o_cost), nv.ptr(ws), nv.stream())
@@ -206,12 +249,19 @@ def backward_grid(disp, T_rel, K, K_inv, baseline):
     return grid
 
 
-def bilinear_sample(img, grid):
+def bilinear_sample(img, grid, start=None):
+    """start: a mixed batch's sequence-start mask [B] (tcs_bilinear_sample_mixed): +0.0 for the start elements, whose img and grid
+    are not read.  None calls tcs_bilinear_sample."""
     B, Cc, Hi, Wi = _dims4(img, "img")
     Bg, two, Ho, Wo = _dims4(grid, "grid")
     if Bg != B or two != 2:
         raise ValueError("grid must be [B,2,Ho,Wo]")
     out = _new(img, B, Cc, Ho, Wo)
+    if start is not None:
+        start = _start(start, B, img.device)
+        nv.check(nv.lib().tcs_bilinear_sample_mixed(nv.ptr(img, "img"), nv.ptr(grid, "grid"), nv.ptr(start, "start", torch.uint8), B, Cc,
+                                                    Hi, Wi, Ho, Wo, nv.ptr(out), nv.stream()), "tcs_bilinear_sample_mixed")
+        return out
     nv.check(nv.lib().tcs_bilinear_sample(nv.ptr(img, "img"), nv.ptr(grid, "grid"), B, Cc, Hi, Wi, Ho, Wo, nv.ptr(out), nv.stream()),
              "tcs_bilinear_sample")
     return out
