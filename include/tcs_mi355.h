@@ -37,7 +37,8 @@ typedef void* tcs_stream_t;
 
 int tcs_abi_version(void);                 /* bumped when a signature changes (7: grouped launches, blend_warm_*; 8: `products`, the
                                               last field of tcs_conv_desc and tcs_conv_s16_desc; 9: the ordered splat entry points;
-                                              10: tcs_conv2d_group_fused; 11: the *_mixed entry points) */
+                                              10: tcs_conv2d_group_fused; 11: the *_mixed entry points;
+                                              12: tcs_convex_upsample_pair, tcs_resize_bilinear_scaled) */
 const char* tcs_error_string(int code);
 
 /* ------------------------------------------------------------------------------------------------
@@ -240,12 +241,23 @@ int tcs_softmax_blend(const float* logits9, const float* cand, int cand_ctot, co
 int tcs_convex_upsample(const float* disp, const float* mask, int B, int H, int W, int clip, float* flow_up, float* flow_q,
                         tcs_stream_t stream);
 
+/* The two upsamplings of one iteration's non-test-mode outputs (tc_stereo.py:204-215), which share that iteration's mask:
+ * disp_a, disp_b [B,1,H,W] (disp_q and refined_disp), mask [B,144,H,W] -> up_a, up_b [B,1,4H,4W] and q_a = -disp_a, q_b = -disp_b
+ * [B,1,H,W].  The mask is read and each output pixel's 9-way softmax computed once for both.  Not clipped.  Each output is
+ * bit-equal to tcs_convex_upsample(..., clip = 0) on that disparity (up_x to its flow_up, q_x to its flow_q).  The outputs are
+ * dense [B,...] blocks and may be slots of larger stacked tensors. */
+int tcs_convex_upsample_pair(const float* disp_a, const float* disp_b, const float* mask, int B, int H, int W, float* up_a, float* up_b,
+                             float* q_a, float* q_b, tcs_stream_t stream);
+
 /* pool2x = avg_pool2d(3, stride 2, pad 1), divisor 9 everywhere (update.py:114-115): [B,C,H,W] -> [B,C,Ho,Wo],
  * Ho = (H-1)/2+1. */
 int tcs_avgpool3s2(const float* x, int B, int C, int H, int W, float* out, tcs_stream_t stream);
 
 /* interp(): bilinear resize with align_corners=True (update.py:122-124): [B,C,H,W] -> [B,C,Ho,Wo]. */
 int tcs_resize_bilinear(const float* x, int B, int C, int H, int W, int Ho, int Wo, float* out, tcs_stream_t stream);
+/* tcs_resize_bilinear times `scale` (the -4 * F.interpolate(., scale_factor=4, bilinear, align_corners=True) of flow_mono /
+ * flow_init, tc_stereo.py:233-234).  With scale = 1 it equals tcs_resize_bilinear; a power-of-two scale scales it exactly. */
+int tcs_resize_bilinear_scaled(const float* x, int B, int C, int H, int W, int Ho, int Wo, float scale, float* out, tcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Convolutions on the matrix cores, fp32 NCHW tensors in and out: fp32 MFMA (TCS_MATH_F32) or fp16-split operands with fp32

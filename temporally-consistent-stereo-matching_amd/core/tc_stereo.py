@@ -8,8 +8,9 @@ image-only stage is enqueued ahead of time).  What differs is underneath: correl
 step, both U-Nets, every stencil and the feature extractor's convolutions are hand-written HIP kernels
 for gfx950 (libtcs_mi355.so); PyTorch-ROCm owns tensors, streams and graph capture.
 
-Inference only: `test_mode=False` (training outputs and losses, train_stereo.py) is out of scope.
-There is no CPU path: tensors must live on a HIP device and the library must be built.
+No autograd: `test_mode=False` returns the reference's training-output dict (every iteration's predictions, the cost volume,
+flow_mono / flow_init) under torch.no_grad() / inference_mode() or with frozen parameters, and raises NotImplementedError when
+gradients would be expected.  There is no CPU path: tensors must live on a HIP device and the library must be built.
 """
 import contextlib
 import os
@@ -195,7 +196,6 @@ class TCStereo(nn.Module):
             raise RuntimeError("TCStereo.prefetch needs HIP device tensors; there is no CPU fallback")
         self._pipeline().prefetch(image1, image2, first=bool(first), use_graph=self._graph_mode(), inputs_ready=bool(inputs_ready))
 
-    @torch.no_grad()
     def forward(self, image1, image2, iters=12, params=None, test_mode=False, frame_id=0):
         """Disparity of a stereo pair, optionally conditioned on the previous frame (`params`):
         K [b,3,3], T / previous_T [b,4,4] world->camera, baseline [b], last_disp (= previous 'flow_q'),
@@ -211,9 +211,24 @@ class TCStereo(nn.Module):
 
         A frame is two fixed launch sequences with no host round trip — the image-only stage (`_extract_stage`) and the
         state-dependent stage (`_refine_stage`) — so by default each is captured once per (shape, iters, branch) into a HIP
-        graph and replayed (tcs_mi355.graph); set TCS_MI355_GRAPH=0 or `model.use_hip_graph = False` for eager launches."""
-        if not test_mode:
-            raise NotImplementedError("TCStereo on MI355X is inference-only: call with test_mode=True")
+        graph and replayed (tcs_mi355.graph); set TCS_MI355_GRAPH=0 or `model.use_hip_graph = False` for eager launches.
+
+        `test_mode=False` returns the reference's training-output dict (tc_stereo.py:229-243) without an autograd graph:
+        'flow_predictions' (`iters` pairs [flows_up, flow_refine_up], the unclipped convex x4 upsamplings of -disp_q and
+        -refined_disp, [b,1,H,W] each), 'flow_q_predictions' (`iters` pairs [-disp_q, -refined_disp], [b,1,H/4,W/4]),
+        'disp_grad_q_predictions' (`iters` refined gradients [b,2,H/4,W/4]), 'flow_mono' / 'flow_init' ([b,1,H,W]), 'cost_volume'
+        ([b,W/4,H/4,W/4], masked) and the same 'flow_q', 'net_list', 'fmap1' as test mode.  The per-iteration entries are views into
+        one stacked tensor per key (e.g. flow_predictions[k][1] is a view of a [iters,2,b,1,H,W] tensor); every call returns fresh
+        storage that no later call overwrites.  It runs under torch.no_grad() / torch.inference_mode() or when no parameter
+        requires grad; otherwise it raises NotImplementedError.  Each iteration's upsampling mask head runs off the critical chain
+        (DESIGN.md section 12)."""
+        if not test_mode and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError("TCStereo on MI355X builds no autograd graph: call test_mode=False under torch.no_grad() (or "
+                                      "torch.inference_mode(), or with every parameter frozen), or use test_mode=True")
+        with torch.no_grad():
+            return self._forward(image1, image2, iters, params, bool(test_mode))
+
+    def _forward(self, image1, image2, iters, params, test_mode):
         if iters < 1:
             raise ValueError("iters must be >= 1")
         if not image1.is_cuda:
@@ -224,20 +239,36 @@ class TCStereo(nn.Module):
                         list(params["last_net_list"]), params["fmap1"])
             if params.get("new_sequence") is not None:          # mixed batch: the mask is the 8th entry
                 temporal = temporal + (sequence_starts(params["new_sequence"], int(image1.shape[0]), image1.device),)
-        return self._pipeline()(image1, image2, iters, temporal, use_graph=self._graph_mode())
+        if test_mode:
+            return self._pipeline()(image1, image2, iters, temporal, use_graph=self._graph_mode())
+        out = self._pipeline()(image1, image2, iters, temporal, use_graph=self._graph_mode(), outputs=True)
+        return self._training_output(out, iters)
 
-    def _frame(self, image1, image2, iters, temporal):
+    @staticmethod
+    def _training_output(out, iters):
+        """The loop's stacked outputs -> the reference's training_output dict (per-iteration entries are views)."""
+        up, q, grad = out["up"], out["q"], out["grad"]
+        return {"flow_mono": out["flow_mono"], "flow_init": out["flow_init"],
+                "flow_predictions": [[up[k, 0], up[k, 1]] for k in range(iters)],
+                "flow_q_predictions": [[q[k, 0], q[k, 1]] for k in range(iters)],
+                "disp_grad_q_predictions": [grad[k] for k in range(iters)],
+                "cost_volume": out["cost_volume"],
+                "flow_q": out["flow_q"], "net_list": out["net_list"], "fmap1": out["fmap1"]}
+
+    def _frame(self, image1, image2, iters, temporal, outputs=False):
         """One frame as a pure launch sequence on the current stream (both stages back to back)."""
-        feats = self._extract_stage(image1, image2, temporal is None or len(temporal) == 8)
-        return self._refine_loop(feats, self._refine_head(feats, temporal), iters)
+        feats = self._extract_stage(image1, image2, temporal is None or len(temporal) == 8, outputs)
+        return self._refine_loop(feats, self._refine_head(feats, temporal), iters, outputs)
 
-    def _extract_stage(self, image1, image2, first):
+    def _extract_stage(self, image1, image2, first, cost_volume=False):
         """Everything of a frame that depends only on its two images (tensors in, tensors out; capturable): matching features,
-        correlation pyramid (+ the arg-max prior on a first frame), per-scale context terms (tc_stereo.py:101-116,147-149)."""
+        correlation pyramid (+ the arg-max prior on a first frame), per-scale context terms (tc_stereo.py:101-116,147-149).
+        `cost_volume`: the build also writes the masked cost volume (test_mode=False's 'cost_volume', corr.py:24-31)."""
         a = self.args
 
         def correlate(fmap1, fmap2):
-            corr_fn = CorrBlock1D(fmap1, fmap2, radius=a.corr_radius, num_levels=a.corr_levels, thres=a.init_thres, want_argmax=first)
+            corr_fn = CorrBlock1D(fmap1, fmap2, radius=a.corr_radius, num_levels=a.corr_levels, thres=a.init_thres, want_argmax=first,
+                                  want_cost_volume=cost_volume)
             return corr_fn, (corr_fn.argmax_disp() if first else None)
 
         def context(cnet_list, relu_done=False):
@@ -295,10 +326,10 @@ class TCStereo(nn.Module):
         pool = self._s16pool
         s16_head = "dc32" not in _X
         if s16_head:
-            disp_init, _, _, net_list = self.disp_completor.run16(pool, sparse_disp, cost, sparse_mask, [c.float().contiguous() for c in net_list],
-                                                                  tanh_nets=True)
+            disp_init, disp_mono, _, net_list = self.disp_completor.run16(pool, sparse_disp, cost, sparse_mask,
+                                                                          [c.float().contiguous() for c in net_list], tanh_nets=True)
         else:
-            disp_init, _, _, net_list = self.disp_completor(sparse_disp, cost, sparse_mask, net_list, tanh_nets=True)
+            disp_init, disp_mono, _, net_list = self.disp_completor(sparse_disp, cost, sparse_mask, net_list, tanh_nets=True)
         disp_init = disp_init.float().contiguous()
 
         if last_net_list is None:
@@ -329,10 +360,12 @@ class TCStereo(nn.Module):
         if trace is not None:
             trace.update(sparse_disp=sparse_disp, cost=cost, sparse_mask=sparse_mask, disp_init=disp_init,
                          net0=[t.float().clone() for t in net_list], iters=[])
-        return {"coords1": coords1, "net_list": net_list}
+        # (disp_init / disp_mono: read only by the outputs mode of the loop, for flow_init / flow_mono)
+        return {"coords1": coords1, "net_list": net_list, "disp_init": disp_init, "disp_mono": disp_mono}
 
-    def _refine_loop(self, feats, start, iters):
-        """The refinement loop and the upsampling (tc_stereo.py:175-229) from the head's disparity / hidden states (capturable)."""
+    def _refine_loop(self, feats, start, iters, outputs=False):
+        """The refinement loop and the upsampling (tc_stereo.py:175-229) from the head's disparity / hidden states (capturable).
+        `outputs` (test_mode=False): also every iteration's predictions, stacked, plus flow_mono / flow_init / cost_volume."""
         a = self.args
         fmap1, corr_fn = feats["fmap1"], feats["corr_fn"]
         inp_list, grad_list = feats["inp_list"], feats["grad_list"]
@@ -365,6 +398,7 @@ class TCStereo(nn.Module):
         hu_delta = None              # the hidden-state update of iteration i-1 runs at the head of iteration i's coarse chain
         early32 = None               # gru32 of iteration i + the early share of gru16, launched during iteration i-1
         plain = not a.slow_fast_gru and n3
+        side = _OutputsSide(self, pool, coords1, iters, start) if outputs else None
         # Schedule of one iteration.  The critical chain — blend(i-1) -> hidden-state update -> pool -> gru16's late
         # share -> interp -> gru08 -> flow head -> gradient predictor -> refinement -> blend(i) — is the FIRST branch of every fork, so
         # that it stays in one launch list of the captured graph (tcs_mi355/streams.py: capture order at a fork); what has slack hangs off it as side
@@ -392,6 +426,8 @@ class TCStereo(nn.Module):
             up32_now = join(early32)                     # (None on the first iteration: gru32 then runs inside the coarse branch)
             early32 = None
             up16, (corr, m) = fork_join([coarse_branch, enc_branch], site="iter")
+            if side is not None:
+                side.launch()                            # the previous iteration's mask head + pair upsampling (behind the blend)
             run_ahead = plain and trace is None and itr + 1 < iters
             # net16 is final for this iteration: gru32 of the NEXT iteration + gru16's early share (update.py) may start from here
             def ahead():
@@ -414,8 +450,14 @@ class TCStereo(nn.Module):
             last = itr == iters - 1
             # (not on the last iteration: no lookup follows; "nowarm": A/B)
             warm = corr_fn._pyr if (not last and "nowarm" not in _X and a.corr_levels == 4) else None
-            refined, up_mask, fused = self.disp_refine.run(pool, disp_grad, disp_q, nets[0], context, want_mask=last, motion=motion,
-                                                           warm_pyramid=warm, warm_radius=a.corr_radius)
+            if side is None:
+                refined, up_mask, fused = self.disp_refine.run(pool, disp_grad, disp_q, nets[0], context, want_mask=last, motion=motion,
+                                                               warm_pyramid=warm, warm_radius=a.corr_radius)
+            else:
+                refined, up_mask, fused = self.disp_refine.run(pool, disp_grad, disp_q, nets[0], context, motion=motion,
+                                                               warm_pyramid=warm, warm_radius=a.corr_radius, grad_out=side.grad[itr],
+                                                               before_fuse=side.join)
+                side.record(itr, disp_q, refined, fused["fused"])
             hu_delta = fused["delta_disp"]
             coords1, flows_x = fused["coords1"], fused["flow_x"]
             if sums is not None:
@@ -429,7 +471,76 @@ class TCStereo(nn.Module):
                                            net=[t.float() for t in nets]))
         if hu_delta is not None:
             self.hiddenstate_update.run(pool, nets[0], hu_delta)
+        if side is not None:
+            side.launch()
+            up_mask = side.join()                        # the last iteration's mask
         net_list = [t.float() for t in nets]
 
         flow_up, flow_q = ops.convex_upsample(refined.contiguous(), up_mask)
-        return {"flow": flow_up, "flow_q": flow_q, "net_list": [x.detach() for x in net_list], "fmap1": fmap1.detach()}
+        out = {"flow": flow_up, "flow_q": flow_q, "net_list": [x.detach() for x in net_list], "fmap1": fmap1.detach()}
+        if side is not None:
+            out.update(side.outputs(corr_fn))
+        return out
+
+
+class _OutputsSide:
+    """The outputs mode of `TCStereo._refine_loop` (test_mode=False).  Every iteration's upsampling mask head
+    (DispRefine.mask_head, 6.4 GMAC at 640x480) and the pair kernel that upsamples disp_q and refined_disp with it only feed outputs, so
+    they run as one side list (`streams.spawn`) per iteration, forked at the iteration's blend and enqueued behind the next launch of
+    the critical chain (the hidden-state update), so that the chain stays its first child (tcs_mi355/streams.py, capture order).
+
+    Hazard: the mask head reads DispRefine's pooled `fused` buffer, which the next iteration's conv_fuse[2] overwrites.  Chosen: the
+    side list is joined right before that write (DispRefine.run(before_fuse=)).  It has the whole next iteration up to conv_fuse
+    (~0.9 of an iteration) to finish, so the join rarely waits, and one join also orders the side lists among themselves, so that
+    one set of side buffers (the mask head's S16 hidden layer, the fp32 mask) serves every iteration.  Two `fused` buffers by parity
+    would change the default path's buffers or add a copy, and would still need a join two iterations later."""
+
+    def __init__(self, model, pool, coords1, iters, start):
+        B, _, H, W = (int(v) for v in coords1.shape)
+        dev = coords1.device
+        self.model, self.pool = model, pool
+        # the stacked outputs: [iters, (disp_q, refined), B, 1, ...] and the refined gradients [iters, B, 2, H, W]
+        self.up = torch.empty(iters, 2, B, 1, 4 * H, 4 * W, dtype=torch.float32, device=dev)
+        self.q = torch.empty(iters, 2, B, 1, H, W, dtype=torch.float32, device=dev)
+        self.grad = torch.empty(iters, B, 2, H, W, dtype=torch.float32, device=dev)
+        self.mask = pool.get32((id(model.disp_refine.mask[2]), "outputs"), (B, 144, H, W), dev)
+        self.flow_mono = torch.empty(B, 1, 4 * H, 4 * W, dtype=torch.float32, device=dev)
+        self.flow_init = torch.empty_like(self.flow_mono)
+        self.disp_mono, self.disp_init = start["disp_mono"].float().contiguous(), start["disp_init"].float().contiguous()
+        self.pending = None         # (fork event, itr, disp_q, refined, fused) recorded at a blend, not yet launched
+        self.running = None         # the spawned side list not yet joined
+        self.keep = []              # every tensor a side list reads stays referenced until the loop's last join (eager allocator)
+
+    def record(self, itr, disp_q, refined, fused):
+        from tcs_mi355.streams import mark
+        self.pending = (mark(), itr, disp_q, refined, fused)
+        self.keep += [disp_q, refined]
+
+    def launch(self):
+        if self.pending is None:
+            return
+        from tcs_mi355.streams import spawn
+        at, itr, disp_q, refined, fused = self.pending
+        self.pending = None
+
+        def side():
+            if itr == 0:            # flow_mono / flow_init (tc_stereo.py:233-234): the head's outputs, ready long since
+                H4, W4 = self.flow_mono.shape[-2:]
+                ops.resize_bilinear(self.disp_mono, H4, W4, out=self.flow_mono, scale=-4.0)
+                ops.resize_bilinear(self.disp_init, H4, W4, out=self.flow_init, scale=-4.0)
+            self.model.disp_refine.mask_head(self.pool, fused, out=self.mask)
+            ops.convex_upsample_pair(disp_q, refined, self.mask, self.up[itr, 0], self.up[itr, 1], self.q[itr, 0], self.q[itr, 1])
+
+        self.running = spawn(side, site="outputs", slot=1, after=at)
+
+    def join(self):
+        from tcs_mi355.streams import join
+        if self.running is not None:
+            join(self.running)
+            self.running = None
+        return self.mask
+
+    def outputs(self, corr_fn):
+        self.keep = []
+        return {"up": self.up, "q": self.q, "grad": self.grad, "flow_mono": self.flow_mono, "flow_init": self.flow_init,
+                "cost_volume": corr_fn.get_cost_volume()}

@@ -687,20 +687,32 @@ class DispRefine(nn.Module):
         cg = to16(pool, context_grad, (id(self), "ctxg_in"))
         refined, mask, extra = self.run(pool, disp_grads.float().contiguous(), disp.float().contiguous(), cd, cg, want_mask=not test_mode)
         if fused_outputs is not None:
-            fused_outputs.update(extra)
+            fused_outputs.update({k: v for k, v in extra.items() if k != "fused"})
         return refined, mask
 
+    def mask_head(self, pool, fused: s16.S16, out: torch.Tensor = None) -> torch.Tensor:
+        """0.25 * mask(fused) (update.py:303-304) -> fp32 [B,144,H,W], into `out` when given.  `fused` is run()'s pooled conv_fuse
+        output (dict key "fused"): it holds this iteration's value until the next run() writes conv_fuse[2] again."""
+        m = conv16(pool, self.mask[0], [fused], act="relu")
+        if out is None:
+            return conv16(pool, self.mask[2], [m], post_scale=0.25, want32=True)
+        return s16.conv2d(packed16(self.mask[2]), [m], post_scale=0.25, out32=out)[1]
+
     def run(self, pool, disp_grads: torch.Tensor, disp: torch.Tensor, context_disp: s16.S16, context_grad: s16.S16, want_mask=False,
-            motion: s16.S16 = None, warm_pyramid=None, warm_radius: int = 4):
-        """-> (refined fp32, mask fp32 or None, dict(delta_disp, coords1, flow_x)).  With `motion`, the next iteration's flow input
-        (coords1 - x) also lands in channel 127 of that S16 buffer (tc_stereo.py:180, update.py:126)."""
+            motion: s16.S16 = None, warm_pyramid=None, warm_radius: int = 4, grad_out: torch.Tensor = None, before_fuse=None):
+        """-> (refined fp32, mask fp32 or None, dict(delta_disp, coords1, flow_x, fused)).  With `motion`, the next iteration's flow input
+        (coords1 - x) also lands in channel 127 of that S16 buffer (tc_stereo.py:180, update.py:126).  `grad_out` ([B,2,H,W] fp32): the
+        refined gradient is also written there.  `before_fuse`: called right before conv_fuse[2] overwrites the pooled `fused` buffer
+        (TCStereo's outputs mode joins the previous iteration's mask head there)."""
         # the candidate stencil (with the residual head's last convolution finished from its tap partials) stays on the chain; behind it
         # the context branch (the longer one) continues the chain and the two 1x1 layers of the candidate stem run beside it
         f27 = pool.get((id(self), "f27"), disp.shape[0], 27, disp.shape[2], disp.shape[3], disp.device)
         if isinstance(disp_grads, tuple):        # (tap partials of residual_head[2], 5*grad, 1/5) from DispGradPredictor.run(lazy=True)
-            f27, cand9, self._last_grad = s16.taps_propagate(disp_grads[0], disp_grads[1], disp_grads[2], disp, out16=f27)
+            f27, cand9, self._last_grad = s16.taps_propagate(disp_grads[0], disp_grads[1], disp_grads[2], disp, out16=f27, grad=grad_out)
         else:
             f27, cand9 = s16.propagate_disparity(disp_grads, disp, out16=f27)
+            if grad_out is not None:
+                grad_out.copy_(disp_grads)
 
         cc, ds = self.context_compress, self.disp_f_stem
         # context_compress (3x3, 192 -> 96 -> 96) beside disp_f_stem (1x1, 27 -> 96 -> 96), layer by layer as grouped launches
@@ -713,6 +725,8 @@ class DispRefine(nn.Module):
             context = conv16(pool, cc[2], [c], tile_cfg=t3)
             disp_f = conv16(pool, ds[2], [d])
         fused = conv16(pool, self.conv_fuse[0], [disp_f, context], act="relu")
+        if before_fuse is not None:
+            before_fuse()
         fused = conv16(pool, self.conv_fuse[2], [fused], act="relu")
         w = conv16(pool, self.w_head[0], [fused], act="relu")
         coords1, flow_x = torch.empty_like(disp), torch.empty_like(disp)
@@ -724,11 +738,8 @@ class DispRefine(nn.Module):
         else:
             logits = conv16(pool, self.w_head[2], [w], want32=True)
             refined, delta = s16.softmax_blend(logits, cand9, disp, coords1, flow_x, flow_x_s16=motion, flow_x_channel=127)
-        mask = None
-        if want_mask:
-            m = conv16(pool, self.mask[0], [fused], act="relu")
-            mask = conv16(pool, self.mask[2], [m], post_scale=0.25, want32=True)
-        return refined, mask, dict(delta_disp=delta, coords1=coords1, flow_x=flow_x)
+        mask = self.mask_head(pool, fused) if want_mask else None
+        return refined, mask, dict(delta_disp=delta, coords1=coords1, flow_x=flow_x, fused=fused)
 
 
 # ---------------------------------------------------------------------------------------------

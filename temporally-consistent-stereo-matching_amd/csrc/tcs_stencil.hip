@@ -218,6 +218,46 @@ __global__ __launch_bounds__(256) void k_convex_upsample(const float* __restrict
     }
 }
 
+// The convex upsampling of TWO disparities with the same mask (tc_stereo.py:204-215: flows_up of -disp_q and flow_refine_up of
+// -refined_disp share the iteration's up_mask): the 9 mask logits of an output pixel are read and soft-maxed once for both.  Unclipped,
+// and each output is bit-equal to k_convex_upsample(clip=0) on that disparity: the same loads and the same operations in the same order.
+__global__ __launch_bounds__(256) void k_convex_upsample_pair(const float* __restrict__ disp_a, const float* __restrict__ disp_b,
+                                                              const float* __restrict__ mask, int H, int W, float* __restrict__ up_a,
+                                                              float* __restrict__ up_b, float* __restrict__ q_a, float* __restrict__ q_b) {
+    const int b = blockIdx.y, HW = H * W;
+    const int Wu = 4 * W, Hu = 4 * H;
+    const int pu = blockIdx.x * 256 + threadIdx.x;
+    if (pu >= Hu * Wu) return;
+    const int yu = pu / Wu, xu = pu - yu * Wu;
+    const int y = yu >> 2, i = yu & 3, x = xu >> 2, j = xu & 3;
+    const float* da = disp_a + (size_t)b * HW;
+    const float* db = disp_b + (size_t)b * HW;
+    const float* mk = mask + ((size_t)b * 144 + i * 4 + j) * HW + y * W + x;
+    float w[9], m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { w[k] = mk[(size_t)k * 16 * HW]; m = fmaxf(m, w[k]); }
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { w[k] = expf(w[k] - m); s += w[k]; }
+    float ra = 0.f, rb = 0.f;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
+        const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
+        const float fa = in ? 4.f * (-da[yy * W + xx]) : 0.f;
+        const float fb = in ? 4.f * (-db[yy * W + xx]) : 0.f;
+        const float wk = w[k] / s;
+        ra += wk * fa;
+        rb += wk * fb;
+    }
+    up_a[(size_t)b * Hu * Wu + pu] = ra;
+    up_b[(size_t)b * Hu * Wu + pu] = rb;
+    if (i == 0 && j == 0) {
+        q_a[(size_t)b * HW + y * W + x] = -da[y * W + x];
+        q_b[(size_t)b * HW + y * W + x] = -db[y * W + x];
+    }
+}
+
 // update.py:114-115: 3x3 stride-2 pad-1 average, divisor always 9
 __global__ __launch_bounds__(256) void k_avgpool3s2(const float* __restrict__ x, int H, int W, int Ho, int Wo, float* __restrict__ out) {
     const int bc = blockIdx.y;
@@ -478,6 +518,15 @@ int tcs_convex_upsample(const float* disp, const float* mask, int B, int H, int 
     return tcs_launch_status();
 }
 
+int tcs_convex_upsample_pair(const float* disp_a, const float* disp_b, const float* mask, int B, int H, int W, float* up_a, float* up_b,
+                             float* q_a, float* q_b, tcs_stream_t stream) {
+    if (!disp_a || !disp_b || !mask || !up_a || !up_b || !q_a || !q_b || B <= 0 || B > 65535 || H <= 0 || W <= 0) return TCS_EINVAL;
+    if ((long long)16 * H * W > 0x7fffffffLL) return TCS_EUNSUPPORTED;
+    hipLaunchKernelGGL(k_convex_upsample_pair, dim3(tcs_cdiv((long long)16 * H * W, 256), B), dim3(256), 0, tcs_stream(stream),
+                       disp_a, disp_b, mask, H, W, up_a, up_b, q_a, q_b);
+    return tcs_launch_status();
+}
+
 int tcs_avgpool3s2(const float* x, int B, int C, int H, int W, float* out, tcs_stream_t stream) {
     if (!x || !out || B <= 0 || C <= 0 || H <= 0 || W <= 0) return TCS_EINVAL;
     if ((long long)B * C > 65535) return TCS_EUNSUPPORTED;
@@ -486,7 +535,7 @@ int tcs_avgpool3s2(const float* x, int B, int C, int H, int W, float* out, tcs_s
     return tcs_launch_status();
 }
 
-int tcs_abi_version(void) { return 11; }
+int tcs_abi_version(void) { return 12; }
 
 const char* tcs_error_string(int code) {
     switch (code) {

@@ -973,4 +973,12 @@ int tcs_resize_bilinear(const float* x, int B, int C, int H, int W, int Ho, int 
     return tcs_launch_status();
 }
 
+int tcs_resize_bilinear_scaled(const float* x, int B, int C, int H, int W, int Ho, int Wo, float scale, float* out, tcs_stream_t stream) {
+    if (!x || !out || B <= 0 || C <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) return TCS_EINVAL;
+    if ((long long)B * C > 65535) return TCS_EUNSUPPORTED;
+    hipLaunchKernelGGL(k_resize_bilinear, dim3(tcs_cdiv((long long)Ho * Wo, 256), B * C), dim3(256), 0, tcs_stream(stream),
+                       x, C, H, W, Ho, Wo, scale, out);
+    return tcs_launch_status();
+}
+
 }  // extern "C"

@@ -11,6 +11,9 @@ the frame's serial path; on the GPU the extraction does NOT run beside the loop 
 frame's last one — the loop's graph occupies the hardware queues).  Without a prefetch the two stages simply run back to back, as
 the reference does.
 
+A `test_mode=False` frame (`outputs=True`: every iteration's predictions, the cost volume) is its own EXTRACT key (the build also writes
+the cost volume) and its own REFINE key (the loop's outputs mode); features prefetched for a test-mode frame are not consumed by it.
+
 Each stage is ~100 / ~1,700 kernel launches with static shapes and no host decision inside, so it is captured once per
 (shape, branch[, iteration count]) and slot into a HIP graph and replayed.  Inputs are copied into the graph's static
 buffers, outputs are cloned out, so callers keep ordinary tensor semantics (the temporal state they pass back next frame
@@ -32,6 +35,10 @@ _CAPTURING = 0          # > 0 while any FrameGraphs capture is recording (FrameG
 # EXTRACT is enqueued on the CALLER's stream.  Rounds 3's second stream could not make it overlap the loop on this stack (module docstring) and
 # measured the same (profiles/r04_ab_logs.txt, r4_k); on the caller's stream there are no cross-stream waits to get wrong, and a prefetch
 # only moves the host's launch work ahead.
+
+
+# what the loop's outputs mode adds to the frame's dict (TCStereo._refine_loop(outputs=True))
+_OUTPUTS_KEYS = ("up", "q", "grad", "flow_mono", "flow_init", "cost_volume")
 
 
 def _flatten(temporal):
@@ -114,7 +121,8 @@ class _Entry:
 
 
 class FrameGraphs:
-    """`extract_fn(image1, image2, first) -> feats`, `head_fn(feats, temporal) -> start`, `loop_fn(feats, start, iters) -> dict`.
+    """`extract_fn(image1, image2, first, outputs) -> feats`, `head_fn(feats, temporal) -> start`, `loop_fn(feats, start, iters, outputs)
+    -> dict` (`outputs`: a test_mode=False frame).
     REFINE is captured as two graphs, the short state-dependent head and the loop, with an event between their launches: a prefetch
     made right after a frame's call waits for THAT event, so the next frame's EXTRACT runs beside this frame's loop and not beside
     its head (a chain of small launches that the extractor's 2 400-workgroup launches would starve).
@@ -186,28 +194,28 @@ class FrameGraphs:
         return self.turn
 
     @staticmethod
-    def _token(image1, image2, first, use_graph):
+    def _token(image1, image2, first, use_graph, outputs=False):
         """Identifies the frame a slot's features belong to: the image tensor OBJECTS (the slot keeps them alive, so their storage
         cannot be handed to other tensors meanwhile — a data_ptr alone can come back with other content), their versions (no
-        in-place write since), the branch and the launch mode."""
-        return (image1, image1._version, image2, image2._version, bool(first), bool(use_graph))
+        in-place write since), the branch, the launch mode and whether the features include the cost volume (`outputs`)."""
+        return (image1, image1._version, image2, image2._version, bool(first), bool(use_graph), bool(outputs))
 
     @staticmethod
     def _same(a, b):
         return a is not None and b is not None and a[0] is b[0] and a[2] is b[2] and a[1] == b[1] and a[3] == b[3] and a[4:] == b[4:]
 
     @staticmethod
-    def _ex_key(image1, first):
-        return (tuple(image1.shape), image1.device.index, bool(first))
+    def _ex_key(image1, first, outputs=False):
+        return (tuple(image1.shape), image1.device.index, bool(first), bool(outputs))
 
     @staticmethod
-    def _rf_key(image1, iters, flat):
-        return (tuple(image1.shape), image1.device.index, int(iters), tuple(tuple(t.shape) for t in flat))
+    def _rf_key(image1, iters, flat, outputs=False):
+        return (tuple(image1.shape), image1.device.index, int(iters), tuple(tuple(t.shape) for t in flat), bool(outputs))
 
     # ---- EXTRACT -------------------------------------------------------------------------------------------------------------
-    def _capture_extract(self, key, image1, image2, first) -> Optional[List[_Entry]]:
+    def _capture_extract(self, key, image1, image2, first, outputs=False) -> Optional[List[_Entry]]:
         static_in = [image1.clone(), image2.clone()]
-        run = lambda: self.extract_fn(static_in[0], static_in[1], first)
+        run = lambda: self.extract_fn(static_in[0], static_in[1], first, outputs)
         # The warm-up and the capture write the model's pool buffers, which every extract key of this shape shares: an EXTRACT still in
         # flight on the extract stream (a prefetch) must be over first, and whatever a slot holds unconsumed is no longer trustworthy.
         for sl in self.slots:
@@ -237,18 +245,18 @@ class FrameGraphs:
             torch.cuda.synchronize()
             return None
 
-    def _launch_extract(self, si: int, image1, image2, first: bool, use_graph: bool, inputs_ready: bool = False):
+    def _launch_extract(self, si: int, image1, image2, first: bool, use_graph: bool, inputs_ready: bool = False, outputs: bool = False):
         """EXTRACT into slot `si` on the extract stream: after the slot's last reader, and after everything queued on the caller's
         stream so far (the images are ready) — or, with `inputs_ready` (the images were complete before the latest frame was
         called), only after that frame's head: the extraction then overlaps its loop."""
         slot = self.slots[si]
         main = torch.cuda.current_stream()
         sx = main
-        key = self._ex_key(image1, first)
+        key = self._ex_key(image1, first, outputs)
         entries = None
         if use_graph:
             if key not in self.ex:
-                self.ex[key] = self._capture_extract(key, image1, image2, first)
+                self.ex[key] = self._capture_extract(key, image1, image2, first, outputs)
             entries = self.ex[key]
         with torch.cuda.stream(sx):
             if entries is not None:
@@ -258,11 +266,11 @@ class FrameGraphs:
                 e.graph.replay()
                 slot.feats = e.static_out
             else:
-                slot.feats = self.extract_fn(image1, image2, first)
+                slot.feats = self.extract_fn(image1, image2, first, outputs)
                 for t in _tensors(slot.feats):       # allocated on the extract stream, read on the caller's: keep the blocks alive for it
                     t.record_stream(main)
             slot.ready.record(sx)
-        slot.token, slot.ex_key, slot.fresh, slot.by_prefetch, slot.age = self._token(image1, image2, first, use_graph), key, True, False, 0
+        slot.token, slot.ex_key, slot.fresh, slot.by_prefetch, slot.age = self._token(image1, image2, first, use_graph, outputs), key, True, False, 0
         self.turn = si ^ 1
 
     def prefetch(self, image1, image2, first: bool = False, use_graph: bool = True, inputs_ready: bool = False) -> int:
@@ -282,13 +290,13 @@ class FrameGraphs:
         return si
 
     # ---- REFINE --------------------------------------------------------------------------------------------------------------
-    def _capture_refine(self, key, image1, image2, iters, flat, first) -> Optional[List[_Entry]]:
-        ex_key = self._ex_key(image1, first)
+    def _capture_refine(self, key, image1, image2, iters, flat, first, outputs=False) -> Optional[List[_Entry]]:
+        ex_key = self._ex_key(image1, first, outputs)
         try:
             for si in (0, 1):                        # both slots need features of this shape / branch to capture against
                 if self.slots[si].feats is None or self.slots[si].ex_key != ex_key or self.ex.get(ex_key) is None \
                         or self.slots[si].feats is not self.ex[ex_key][si].static_out:
-                    self._launch_extract(si, image1, image2, first, True)
+                    self._launch_extract(si, image1, image2, first, True, outputs=outputs)
             if self.ex.get(ex_key) is None:
                 return None                          # the extract stage runs eagerly: so does this one
             torch.cuda.synchronize()
@@ -296,7 +304,7 @@ class FrameGraphs:
             entries = []
             for si in (0, 1):
                 feats = self.ex[ex_key][si].static_out
-                run = lambda: self.loop_fn(feats, self.head_fn(feats, _unflatten(static_in)), iters)
+                run = lambda: self.loop_fn(feats, self.head_fn(feats, _unflatten(static_in)), iters, outputs)
                 side = torch.cuda.Stream()
                 side.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(side):
@@ -309,7 +317,7 @@ class FrameGraphs:
                     start = self.head_fn(feats, _unflatten(static_in))
                 g1.replay()                               # (the loop graph is captured against the head graph's output tensors)
                 with _no_gc(), torch.cuda.graph(g2):
-                    out = self.loop_fn(feats, start, iters)
+                    out = self.loop_fn(feats, start, iters, outputs)
                 g2.replay()
                 entries.append(_Entry(g1, static_in, out, graph2=g2))
                 entries[-1].start = start                 # (the loop graph holds raw pointers to the head graph's outputs)
@@ -325,16 +333,18 @@ class FrameGraphs:
             torch.cuda.synchronize()
             return None
 
-    def __call__(self, image1, image2, iters, temporal, use_graph: bool = True):
+    def __call__(self, image1, image2, iters, temporal, use_graph: bool = True, outputs: bool = False):
+        """One frame.  `outputs` (a test_mode=False call): the loop's outputs mode on features extracted with the cost volume; the
+        returned dict then also holds the loop's stacked per-iteration tensors, flow_mono, flow_init and cost_volume, all cloned."""
         self._check_epoch()
         flat = _flatten(temporal)
         first = _wants_argmax(temporal)
-        token = self._token(image1, image2, first, use_graph)
+        token = self._token(image1, image2, first, use_graph, outputs)
         entries = None
         if use_graph:
-            key = self._rf_key(image1, iters, flat)
+            key = self._rf_key(image1, iters, flat, outputs)
             if key not in self.rf:
-                self.rf[key] = self._capture_refine(key, image1, image2, iters, flat, first)
+                self.rf[key] = self._capture_refine(key, image1, image2, iters, flat, first, outputs)
             entries = self.rf[key]
             if entries is None:
                 self.fell_back += 1
@@ -349,7 +359,7 @@ class FrameGraphs:
             self.prefetched += int(self.slots[si].by_prefetch)
         else:
             si = self._pick_slot()
-            self._launch_extract(si, image1, image2, first, use_graph and entries is not None)
+            self._launch_extract(si, image1, image2, first, use_graph and entries is not None, outputs=outputs)
         slot = self.slots[si]
         slot.fresh, slot.token = False, None            # consumed (and the image tensors are no longer held)
         main = torch.cuda.current_stream()
@@ -364,10 +374,16 @@ class FrameGraphs:
             o = e.static_out
             out = {"flow": o["flow"].clone(), "flow_q": o["flow_q"].clone(), "net_list": [t.clone() for t in o["net_list"]],
                    "fmap1": o["fmap1"].clone()}
+            for k in _OUTPUTS_KEYS if outputs else ():
+                out[k] = o[k].clone()
         else:
             start = self.head_fn(slot.feats, temporal)
             self.loop_start.record(main)
-            out = self.loop_fn(slot.feats, start, iters)
-            out = dict(out, fmap1=out["fmap1"].clone())      # the slot's tensor is overwritten two frames from now
+            if outputs:
+                out = self.loop_fn(slot.feats, start, iters, True)
+                out = dict(out, fmap1=out["fmap1"].clone(), cost_volume=out["cost_volume"].clone())   # (both belong to the slot)
+            else:
+                out = self.loop_fn(slot.feats, start, iters)
+                out = dict(out, fmap1=out["fmap1"].clone())      # the slot's tensor is overwritten two frames from now
         slot.free.record(main)
         return out

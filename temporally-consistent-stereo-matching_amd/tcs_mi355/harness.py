@@ -66,6 +66,13 @@ class FrameStats:
 class SequenceStats:
     frames: List[FrameStats] = field(default_factory=list)
     domain_flags: int = 0        # tcs_s16_flags after the sequence: bit 0 = an activation was clamped at +-65504, bit 1 = NaN / Inf seen
+    # run_sequence(per_iteration=True): per_iteration[f][k] = frame_metrics of scored frame f (aligned with `frames`) after iteration k+1
+    per_iteration: List[List[FrameStats]] = field(default_factory=list)
+
+    def iteration_epe(self) -> np.ndarray:
+        """Mean EPE over the scored frames at every iteration count: [iters] (empty without per_iteration)."""
+        rows = [[f.epe for f in fr] for fr in self.per_iteration]
+        return np.array(rows, np.float64).mean(0) if rows else np.zeros(0, np.float64)
 
     def vector(self) -> np.ndarray:
         """[sum_epe, sum_d1w, sum_d3w, sum_rate, n_frames]: what one rank contributes to the gather."""
@@ -99,10 +106,16 @@ def reduce_stats(vectors: Seq[np.ndarray]) -> Dict[str, float]:
 
 @torch.no_grad()
 def run_sequence(forward: Callable, seq, iters: int, device, temporal: bool = True, divis_by: int = 32,
-                 collect: Optional[list] = None) -> SequenceStats:
+                 collect: Optional[list] = None, per_iteration: bool = False) -> SequenceStats:
     """One video sequence through `forward(image1, image2, iters=, test_mode=True, params=)`.
     State is reset per sequence (evaluate_stereo.py:170-174) and carried frame to frame
-    (evaluate_stereo.py:182-197).  `collect`, if given, receives each frame's unpadded prediction."""
+    (evaluate_stereo.py:182-197).  `collect`, if given, receives each frame's unpadded prediction.
+
+    `per_iteration=True`: every frame is called with test_mode=False under torch.no_grad() and `stats.per_iteration[f][k]` gets the
+    metrics of clip(flow_predictions[k][1], max=0), k = 0 .. iters-1 (the frame's own metrics are those of the last entry, which
+    equals test mode's 'flow').  The state carried forward (flow_q, net_list, fmap1) is the N-iteration one, as in test mode.  So
+    entry k of a frame is what a (k+1)-iteration run of THAT frame gives, given the N-iteration history of the frames before it —
+    not a sequence run with k+1 iterations throughout (from the second frame on the two differ)."""
     stats = SequenceStats()
     K_raw = torch.as_tensor(seq.K, dtype=torch.float32, device=device)[None]
     baseline = torch.tensor([seq.baseline], dtype=torch.float32, device=device)
@@ -116,14 +129,23 @@ def run_sequence(forward: Callable, seq, iters: int, device, temporal: bool = Tr
         padder = InputPadder(im1.shape, divis_by=divis_by)
         (im1, im2), K = padder.pad(im1, im2, K=K_raw)
         params.update(K=K, T=T, previous_T=prev_T, last_disp=flow_q, last_net_list=nets, fmap1=fmap1, baseline=baseline)
-        out = forward(im1, im2, iters=iters, test_mode=True, params=params if (flow_q is not None and temporal) else None)
+        call_params = params if (flow_q is not None and temporal) else None
+        if per_iteration:
+            with torch.no_grad():
+                out = forward(im1, im2, iters=iters, test_mode=False, params=call_params)
+            curve = [frame_metrics(padder.unpad(-torch.clip(p[1], max=0)), gt) for p in out["flow_predictions"]]
+            disp_pr = padder.unpad(-torch.clip(out["flow_predictions"][-1][1], max=0))
+        else:
+            out = forward(im1, im2, iters=iters, test_mode=True, params=call_params)
+            disp_pr = padder.unpad(-out["flow"])
         flow_q, nets, fmap1, prev_T = out["flow_q"], out["net_list"], out["fmap1"], T
-        disp_pr = padder.unpad(-out["flow"])
         if collect is not None:
             collect.append(disp_pr)
         fs = frame_metrics(disp_pr, gt)
         if fs is not None:
             stats.frames.append(fs)
+            if per_iteration:
+                stats.per_iteration.append(curve)
     if torch.device(device).type == "cuda":
         # the device-side replacement of the reference's per-iteration NaN asserts: one read per sequence
         from . import s16

@@ -102,8 +102,10 @@ SIGNATURES = {
     "tcs_propagate_disparity": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp]),
     "tcs_softmax_blend": (c_int, [c_fp, c_fp, c_int, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_longlong, c_fp]),
     "tcs_convex_upsample": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp]),
+    "tcs_convex_upsample_pair": (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "tcs_avgpool3s2": (c_int, [c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp]),
     "tcs_resize_bilinear": (c_int, [c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp]),
+    "tcs_resize_bilinear_scaled": (c_int, [c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_fp, c_fp]),
     "tcs_conv_packed_floats": (c_sz, [c_int, c_int, c_int]),
     "tcs_pack_conv_weight": (c_int, [c_fp, c_int, c_int, c_int, c_fp, c_fp]),
     "tcs_conv_packed_floats_f16x3": (c_sz, [c_int, c_int, c_int]),

@@ -348,6 +348,29 @@ def convex_upsample(disp, mask, clip=True):
     return up, fq
 
 
+def convex_upsample_pair(disp_a, disp_b, mask, up_a=None, up_b=None, q_a=None, q_b=None):
+    """The unclipped x4 convex upsamplings of two disparities that share one mask (the two predictions of one iteration,
+    tc_stereo.py:204-215) -> (up_a, up_b [B,1,4H,4W], q_a = -disp_a, q_b = -disp_b [B,1,H,W]).  Each output is bit-equal to
+    `convex_upsample(disp_x, mask, clip=False)`.  Outputs may be given (contiguous float32 tensors of those shapes, e.g. slots of
+    stacked per-iteration tensors); the missing ones are allocated."""
+    B, _, H, W = _dims4(disp_a, "disp_a")
+    if tuple(disp_b.shape) != (B, 1, H, W) or tuple(disp_a.shape) != (B, 1, H, W):
+        raise ValueError("disp_a and disp_b must both be [B,1,H,W]")
+    if tuple(mask.shape) != (B, 144, H, W):
+        raise ValueError("mask must be [B,144,H,W] (factor 4)")
+    outs = []
+    for t, shape, name in ((up_a, (B, 1, 4 * H, 4 * W), "up_a"), (up_b, (B, 1, 4 * H, 4 * W), "up_b"), (q_a, (B, 1, H, W), "q_a"),
+                           (q_b, (B, 1, H, W), "q_b")):
+        if t is None:
+            t = _new(disp_a, *shape)
+        elif tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape}")
+        outs.append(t)
+    nv.check(nv.lib().tcs_convex_upsample_pair(nv.ptr(disp_a, "disp_a"), nv.ptr(disp_b, "disp_b"), nv.ptr(mask, "mask"), B, H, W,
+                                               *(nv.ptr(t) for t in outs), nv.stream()), "tcs_convex_upsample_pair")
+    return tuple(outs)
+
+
 def avgpool3s2(x, out=None):
     B, Cc, H, W = _dims4(x, "x")
     out = _new(x, B, Cc, (H - 1) // 2 + 1, (W - 1) // 2 + 1) if out is None else out
@@ -355,10 +378,16 @@ def avgpool3s2(x, out=None):
     return out
 
 
-def resize_bilinear(x, Ho: int, Wo: int, out=None):
+def resize_bilinear(x, Ho: int, Wo: int, out=None, scale=None):
+    """Bilinear resize with align_corners=True, [B,C,H,W] -> [B,C,Ho,Wo]; `scale` (a float) multiplies the result in the same launch
+    (flow_mono / flow_init: scale=-4).  scale=None is the plain resize."""
     B, Cc, H, W = _dims4(x, "x")
     out = _new(x, B, Cc, Ho, Wo) if out is None else out
-    nv.check(nv.lib().tcs_resize_bilinear(nv.ptr(x, "x"), B, Cc, H, W, Ho, Wo, nv.ptr(out), nv.stream()), "tcs_resize_bilinear")
+    if scale is None:
+        nv.check(nv.lib().tcs_resize_bilinear(nv.ptr(x, "x"), B, Cc, H, W, Ho, Wo, nv.ptr(out), nv.stream()), "tcs_resize_bilinear")
+    else:
+        nv.check(nv.lib().tcs_resize_bilinear_scaled(nv.ptr(x, "x"), B, Cc, H, W, Ho, Wo, float(scale), nv.ptr(out), nv.stream()),
+                 "tcs_resize_bilinear_scaled")
     return out
 
 
