@@ -38,7 +38,7 @@ typedef void* tcs_stream_t;
 int tcs_abi_version(void);                 /* bumped when a signature changes (7: grouped launches, blend_warm_*; 8: `products`, the
                                               last field of tcs_conv_desc and tcs_conv_s16_desc; 9: the ordered splat entry points;
                                               10: tcs_conv2d_group_fused; 11: the *_mixed entry points;
-                                              12: tcs_convex_upsample_pair, tcs_resize_bilinear_scaled) */
+                                              12: tcs_convex_upsample_pair, tcs_resize_bilinear_scaled; 13: the tcs_*loss* entry points) */
 const char* tcs_error_string(int code);
 
 /* ------------------------------------------------------------------------------------------------
@@ -538,6 +538,62 @@ int tcs_conv2d_s16(const tcs_conv_s16_desc* desc, tcs_stream_t stream);
  * descriptors would run as one launch (no launch is made). */
 int tcs_conv2d_s16_group(const tcs_conv_s16_desc* const* descs, int n, tcs_stream_t stream);
 int tcs_conv2d_s16_group_fused(const tcs_conv_s16_desc* const* descs, int n);
+
+/* ------------------------------------------------------------------------------------------------
+ * The training objective (train_stereo.py:41-180, 362-399): targets, the four losses, metrics
+ *
+ * Scale 1/4 only (n_downsample 2): quarter-resolution maps are [B,*,H/4,W/4] (floor).  Per-element arithmetic is fp32 in the reference's
+ * order with no FMA contraction; sums are fp64, written per block to `workspace` (tcs_loss_workspace_bytes; one workspace holds the
+ * partials of every loss of a call) and finished in a fixed order by tcs_loss_finish, so that two calls are bit-equal.
+ * valid_mode: 0 = float32 values as given, 1 = the trainer's rule (valid >= 0.5) & (|flow| < 700) on the dataset's float32 valid,
+ * 2 = a bool / uint8 mask.  The valid map is [B,1,H,W] (or [B,H,W]); masks out are uint8.
+ * ------------------------------------------------------------------------------------------------ */
+#define TCS_LOSS_MAX_ITERS 64
+#define TCS_LOSS_SEQ 1          /* `parts` bits of tcs_loss_finish */
+#define TCS_LOSS_INIT 2
+#define TCS_LOSS_GRAD 4
+#define TCS_LOSS_NORM 8
+/* tcs_loss_finish's fp64 output vector; a loss whose part is absent is NaN, as is a mean over an empty mask.  out32 holds the first
+ * five in fp32.  FLAGS: bit 0 a non-finite flow prediction (or NaN flow_init / flow_mono), bit 1 a non-finite cost volume entry,
+ * bit 2 a non-finite gradient prediction */
+#define TCS_LOSS_OUT_TOTAL 0    /* seq + init + 0.25 norm + 5 grad */
+#define TCS_LOSS_OUT_SEQ 1
+#define TCS_LOSS_OUT_INIT 2
+#define TCS_LOSS_OUT_NORM 3
+#define TCS_LOSS_OUT_GRAD 4
+#define TCS_LOSS_OUT_EPE 5      /* epe, epe_refine, epe_init, 1px, 3px, 5px, 1px_refine, 3px_refine, 5px_refine: 5 .. 13 */
+#define TCS_LOSS_OUT_INIT_GT 14
+#define TCS_LOSS_OUT_INIT_NM 15
+#define TCS_LOSS_OUT_FMR 16     /* forward_mask_rate */
+#define TCS_LOSS_OUT_FLAGS 17
+#define TCS_LOSS_NOUT 18
+
+size_t tcs_loss_workspace_bytes(int B, int H, int W, int iters);
+/* flow_gt [B,1,H,W] + valid -> the median-pooled gradient of -flow [B,2,h,w] and its normal [B,3,h,w] (MedianPool2d(4,4): the lower
+ * median of each 4x4 window, bit-equal to torch), their GT masks (< 5; n_x/n_z, n_y/n_z < 5), max_pool2d(valid, 4) != 0 (dense) and
+ * bilinear(valid, align_corners=True) == 1 (sparse).  The full-resolution gradient is never written. */
+int tcs_loss_targets(const float* flow_gt, const void* valid, int valid_mode, int B, int H, int W, float* grad_gt, float* norm_gt,
+                     uint8_t* grad_mask, uint8_t* norm_mask, uint8_t* valid_dense, uint8_t* valid_sparse, tcs_stream_t stream);
+/* the same from a full-resolution GT [B,C,H,W]: C = 2 gradients, C = 3 normals (valid_mode 0 or 2) */
+int tcs_loss_targets_full(const float* gt, int C, const void* valid, int valid_mode, int B, int H, int W, float* out, uint8_t* gt_mask,
+                          uint8_t* valid_dense, uint8_t* valid_sparse, tcs_stream_t stream);
+/* sequence_loss: iteration i's flow_q-upsampled prediction at preds + i * iter_stride, its refined one at + refine_offset (floats;
+ * [B,1,H,W] each) */
+int tcs_sequence_loss(const float* preds, long long iter_stride, long long refine_offset, int iters, const float* flow_gt,
+                      const void* valid, int valid_mode, const float* flow_mono, const float* flow_init, int B, int H, int W,
+                      double* workspace, tcs_stream_t stream);
+/* init_loss on cost_volume [B,D,H/4,W/4], the top-k of the masked, zero-filled candidates (1 <= k <= min(8, D)); `iters` locates the
+ * partials in the workspace */
+int tcs_init_loss(const float* cost_volume, int D, const float* flow_gt, const void* valid, int valid_mode, int B, int H, int W, int k,
+                  float threshold, int iters, double* workspace, tcs_stream_t stream);
+/* disp_grad_loss (grad_preds: iteration i [B,2,h,w] at + i * grad_stride) and disp_normal_loss (q_preds: flow_q at + i * q_stride,
+ * flow_q_refine at + q_refine_offset, [B,1,h,w]); either may be NULL.  *_valid: the dense or sparse mask of tcs_loss_targets* */
+int tcs_grad_normal_loss(const float* grad_preds, long long grad_stride, const float* q_preds, long long q_stride, long long q_refine_offset,
+                         int iters, const float* grad_gt, const uint8_t* grad_mask, const uint8_t* grad_valid, const float* norm_gt,
+                         const uint8_t* norm_mask, const uint8_t* norm_valid, int B, int H, int W, double* workspace, tcs_stream_t stream);
+/* the partials of `parts` -> out [TCS_LOSS_NOUT] (fp64) and out32 [5]; loss_weights: a HOST array of `iters` doubles */
+int tcs_loss_finish(const double* workspace, int parts, int B, int H, int W, int iters, int k, const double* loss_weights, double* out,
+                    float* out32, tcs_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -68,6 +68,8 @@ class SequenceStats:
     domain_flags: int = 0        # tcs_s16_flags after the sequence: bit 0 = an activation was clamped at +-65504, bit 1 = NaN / Inf seen
     # run_sequence(per_iteration=True): per_iteration[f][k] = frame_metrics of scored frame f (aligned with `frames`) after iteration k+1
     per_iteration: List[List[FrameStats]] = field(default_factory=list)
+    # run_sequence(objective=True): objective[f] = training_objective's metrics dict of frame f (every frame, scored or not)
+    objective: List[Dict[str, float]] = field(default_factory=list)
 
     def iteration_epe(self) -> np.ndarray:
         """Mean EPE over the scored frames at every iteration count: [iters] (empty without per_iteration)."""
@@ -106,7 +108,7 @@ def reduce_stats(vectors: Seq[np.ndarray]) -> Dict[str, float]:
 
 @torch.no_grad()
 def run_sequence(forward: Callable, seq, iters: int, device, temporal: bool = True, divis_by: int = 32,
-                 collect: Optional[list] = None, per_iteration: bool = False) -> SequenceStats:
+                 collect: Optional[list] = None, per_iteration: bool = False, objective: bool = False) -> SequenceStats:
     """One video sequence through `forward(image1, image2, iters=, test_mode=True, params=)`.
     State is reset per sequence (evaluate_stereo.py:170-174) and carried frame to frame
     (evaluate_stereo.py:182-197).  `collect`, if given, receives each frame's unpadded prediction.
@@ -115,7 +117,11 @@ def run_sequence(forward: Callable, seq, iters: int, device, temporal: bool = Tr
     metrics of clip(flow_predictions[k][1], max=0), k = 0 .. iters-1 (the frame's own metrics are those of the last entry, which
     equals test mode's 'flow').  The state carried forward (flow_q, net_list, fmap1) is the N-iteration one, as in test mode.  So
     entry k of a frame is what a (k+1)-iteration run of THAT frame gives, given the N-iteration history of the frames before it —
-    not a sequence run with k+1 iterations throughout (from the second frame on the two differ)."""
+    not a sequence run with k+1 iterations throughout (from the second frame on the two differ).
+
+    `objective=True` (needs iters >= 2): every frame is called with test_mode=False under torch.no_grad() and scored with
+    tcs_mi355.losses.training_objective against its disp_gt (flow = -disp_gt, valid where |disp_gt| < 192; the padding is
+    invalid); `stats.objective[f]` gets the metrics dict plus 'loss'."""
     stats = SequenceStats()
     K_raw = torch.as_tensor(seq.K, dtype=torch.float32, device=device)[None]
     baseline = torch.tensor([seq.baseline], dtype=torch.float32, device=device)
@@ -130,10 +136,20 @@ def run_sequence(forward: Callable, seq, iters: int, device, temporal: bool = Tr
         (im1, im2), K = padder.pad(im1, im2, K=K_raw)
         params.update(K=K, T=T, previous_T=prev_T, last_disp=flow_q, last_net_list=nets, fmap1=fmap1, baseline=baseline)
         call_params = params if (flow_q is not None and temporal) else None
-        if per_iteration:
+        if per_iteration or objective:
             with torch.no_grad():
                 out = forward(im1, im2, iters=iters, test_mode=False, params=call_params)
+        if objective:
+            from .losses import training_objective
+            pads = [padder.left, padder.right, padder.top, padder.bottom]
+            flow_gt = F.pad(-gt.float(), pads)                     # gt: [1,1,H,W]
+            valid = F.pad((gt.abs() < 192.0).float(), pads)
+            total, metrics = training_objective(out, flow_gt.contiguous(), valid.contiguous())
+            stats.objective.append({"loss": float(total), **metrics})
+        if per_iteration:
             curve = [frame_metrics(padder.unpad(-torch.clip(p[1], max=0)), gt) for p in out["flow_predictions"]]
+            disp_pr = padder.unpad(-torch.clip(out["flow_predictions"][-1][1], max=0))
+        elif objective:
             disp_pr = padder.unpad(-torch.clip(out["flow_predictions"][-1][1], max=0))
         else:
             out = forward(im1, im2, iters=iters, test_mode=True, params=call_params)

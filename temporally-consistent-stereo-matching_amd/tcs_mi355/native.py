@@ -142,6 +142,15 @@ SIGNATURES = {
     "tcs_pack_weight_frags": (c_int, [c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp]),
     "tcs_hidden_update_s16": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_f, c_fp, c_fp, c_f, c_fp, c_fp, c_f, c_int, c_int, c_int, c_fp]),
     "tcs_softmax_blend_s16": (c_int, [c_fp, c_fp, c_int, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp]),
+    "tcs_loss_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
+    "tcs_loss_targets": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "tcs_loss_targets_full": (c_int, [c_fp, c_int, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "tcs_sequence_loss": (c_int, [c_fp, C.c_longlong, C.c_longlong, c_int, c_fp, c_fp, c_int, c_fp, c_fp, c_int, c_int, c_int, c_fp,
+                                  c_fp]),
+    "tcs_init_loss": (c_int, [c_fp, c_int, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_f, c_int, c_fp, c_fp]),
+    "tcs_grad_normal_loss": (c_int, [c_fp, C.c_longlong, c_fp, C.c_longlong, C.c_longlong, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
+                                     c_int, c_int, c_int, c_fp, c_fp]),
+    "tcs_loss_finish": (c_int, [c_fp, c_int, c_int, c_int, c_int, c_int, c_int, C.POINTER(C.c_double), c_fp, c_fp, c_fp]),
 }
 
 

@@ -640,3 +640,101 @@ def gru_update(pc_q: PackedConv, srcs, h, z, cq=None, keep_z: bool = False, out=
     d.out, d.out_ctot, d.out_coff = nv.ptr(out, "out"), pc_q.cout, 0
     nv.check(nv.lib().tcs_conv2d(C.byref(d), nv.stream()), "tcs_conv2d[gru_q]")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# the training objective (tcs_loss.hip; tcs_mi355.losses is the reference-shaped surface)
+# ---------------------------------------------------------------------------------------------
+# the order of tcs_loss_finish's output vector (TCS_LOSS_OUT_* in include/tcs_mi355.h)
+LOSS_KEYS = ("loss", "seq_loss", "init_loss", "norm_loss", "grad_loss", "epe", "epe_refine", "epe_init", "1px", "3px", "5px",
+             "1px_refine", "3px_refine", "5px_refine", "init_gt_loss", "init_nm_loss", "forward_mask_rate", "nonfinite")
+LOSS_SEQ, LOSS_INIT, LOSS_GRAD, LOSS_NORM = 1, 2, 4, 8
+LOSS_MAX_ITERS, LOSS_MAX_K = 64, 8
+VALID_VALUES, VALID_TRAINER, VALID_BOOL = 0, 1, 2      # valid_mode of the tcs_*loss* entry points
+
+
+def _u8(t: torch.Tensor) -> torch.Tensor:
+    return t.view(torch.uint8) if t.dtype == torch.bool else t
+
+
+def _valid_ptr(valid: torch.Tensor, mode: int):
+    return nv.ptr(_u8(valid), "valid", torch.uint8 if mode == VALID_BOOL else torch.float32)
+
+
+def loss_workspace(B: int, H: int, W: int, iters: int, device) -> torch.Tensor:
+    """The fp64 partial-sum buffer one objective call (any subset of the four losses) writes."""
+    n = nv.lib().tcs_loss_workspace_bytes(B, H, W, iters)
+    if n == 0:
+        raise ValueError(f"unsupported loss shape B={B} H={H} W={W} iters={iters} (H, W >= 4; 1 <= iters <= {LOSS_MAX_ITERS})")
+    return torch.empty(n // 8, dtype=torch.float64, device=device)
+
+
+def loss_targets(flow_gt: torch.Tensor, valid: torch.Tensor, valid_mode: int = VALID_TRAINER):
+    """flow_gt [B,1,H,W] + valid [B,(1,)H,W] -> the quarter-resolution targets of train_stereo.py:369-376 and :46-53, 72-78:
+    (grad_gt [B,2,h,w], norm_gt [B,3,h,w], grad_mask, norm_mask, valid_dense, valid_sparse [B,1,h,w] bool), h = H // 4."""
+    B, _, H, W = _dims4(flow_gt, "flow_gt")
+    h, w = H // 4, W // 4
+    dev = flow_gt.device
+    grad = torch.empty(B, 2, h, w, dtype=torch.float32, device=dev)
+    norm = torch.empty(B, 3, h, w, dtype=torch.float32, device=dev)
+    masks = [torch.empty(B, 1, h, w, dtype=torch.bool, device=dev) for _ in range(4)]
+    nv.check(nv.lib().tcs_loss_targets(nv.ptr(flow_gt, "flow_gt"), _valid_ptr(valid, valid_mode), valid_mode, B, H, W, nv.ptr(grad),
+                                       nv.ptr(norm), *(nv.ptr(_u8(m), dtype=torch.uint8) for m in masks), nv.stream()), "tcs_loss_targets")
+    return (grad, norm, *masks)
+
+
+def loss_targets_full(gt: torch.Tensor, valid: torch.Tensor, valid_mode: int = VALID_VALUES):
+    """A full-resolution GT [B,C,H,W] (C = 2 gradients, 3 normals) -> (median-pooled GT [B,C,h,w], GT mask, valid_dense, valid_sparse)."""
+    B, Cc, H, W = _dims4(gt, "gt")
+    h, w = H // 4, W // 4
+    dev = gt.device
+    out = torch.empty(B, Cc, h, w, dtype=torch.float32, device=dev)
+    masks = [torch.empty(B, 1, h, w, dtype=torch.bool, device=dev) for _ in range(3)]
+    nv.check(nv.lib().tcs_loss_targets_full(nv.ptr(gt, "gt"), Cc, _valid_ptr(valid, valid_mode), valid_mode, B, H, W, nv.ptr(out),
+                                            *(nv.ptr(_u8(m), dtype=torch.uint8) for m in masks), nv.stream()), "tcs_loss_targets_full")
+    return (out, *masks)
+
+
+def sequence_loss_partials(preds: torch.Tensor, flow_gt, valid, valid_mode: int, flow_mono, flow_init, ws: torch.Tensor):
+    """preds: the stacked [iters, 2, B, 1, H, W] predictions (contiguous) -> the sequence loss's partials in `ws`."""
+    iters, _, B, _, H, W = (int(s) for s in preds.shape)
+    n = B * H * W
+    nv.check(nv.lib().tcs_sequence_loss(nv.ptr(preds, "preds"), 2 * n, n, iters, nv.ptr(flow_gt, "flow_gt"), _valid_ptr(valid, valid_mode),
+                                        valid_mode, nv.ptr(flow_mono, "flow_mono"), nv.ptr(flow_init, "flow_init"), B, H, W,
+                                        nv.ptr(ws, "workspace", torch.float64), nv.stream()), "tcs_sequence_loss")
+
+
+def init_loss_partials(cost_volume, flow_gt, valid, valid_mode: int, k: int, threshold: float, iters: int, ws: torch.Tensor):
+    B, D = int(cost_volume.shape[0]), int(cost_volume.shape[1])
+    H, W = int(flow_gt.shape[2]), int(flow_gt.shape[3])
+    nv.check(nv.lib().tcs_init_loss(nv.ptr(cost_volume, "cost_volume"), D, nv.ptr(flow_gt, "flow_gt"), _valid_ptr(valid, valid_mode),
+                                    valid_mode, B, H, W, int(k), float(threshold), int(iters), nv.ptr(ws, "workspace", torch.float64),
+                                    nv.stream()), "tcs_init_loss")
+
+
+def grad_normal_loss_partials(grad_preds, q_preds, grad_t, norm_t, ws: torch.Tensor, H: int, W: int):
+    """grad_preds: stacked [iters, B, 2, h, w] or None; q_preds: stacked [iters, 2, B, 1, h, w] or None;
+    grad_t / norm_t: (gt, gt_mask, valid_mask) or None."""
+    ref = grad_preds if grad_preds is not None else q_preds
+    iters = int(ref.shape[0])
+    B, h, w = int(ref.shape[-4] if grad_preds is None else ref.shape[1]), int(ref.shape[-2]), int(ref.shape[-1])
+    nq = B * h * w
+    g = grad_t if grad_t is not None else (None, None, None)
+    m = norm_t if norm_t is not None else (None, None, None)
+    u8 = torch.uint8
+    nv.check(nv.lib().tcs_grad_normal_loss(nv.ptr(grad_preds, "disp_grad_preds"), 2 * nq, nv.ptr(q_preds, "flow_q_preds"), 2 * nq, nq,
+                                           iters, nv.ptr(g[0], "grad_gt"), nv.ptr(_u8(g[1]) if g[1] is not None else None, dtype=u8),
+                                           nv.ptr(_u8(g[2]) if g[2] is not None else None, dtype=u8), nv.ptr(m[0], "norm_gt"),
+                                           nv.ptr(_u8(m[1]) if m[1] is not None else None, dtype=u8),
+                                           nv.ptr(_u8(m[2]) if m[2] is not None else None, dtype=u8), B, H, W,
+                                           nv.ptr(ws, "workspace", torch.float64), nv.stream()), "tcs_grad_normal_loss")
+
+
+def loss_finish(ws: torch.Tensor, parts: int, B: int, H: int, W: int, iters: int, k: int, weights):
+    """The partials of `parts` -> (out [len(LOSS_KEYS)] float64, out32 [5] float32: loss, seq, init, norm, grad) on the device."""
+    w = (C.c_double * max(iters, 1))(*[float(x) for x in weights]) if weights is not None else None
+    out = torch.empty(len(LOSS_KEYS), dtype=torch.float64, device=ws.device)
+    out32 = torch.empty(5, dtype=torch.float32, device=ws.device)
+    nv.check(nv.lib().tcs_loss_finish(nv.ptr(ws, "workspace", torch.float64), int(parts), B, H, W, int(iters), int(k), w,
+                                      nv.ptr(out, dtype=torch.float64), nv.ptr(out32), nv.stream()), "tcs_loss_finish")
+    return out, out32

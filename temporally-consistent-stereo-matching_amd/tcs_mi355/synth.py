@@ -155,3 +155,53 @@ def make_sequence(seed: int, n_frames: int = 10, height: int = 480, width: int =
 def make_pair(seed: int, height: int = 240, width: int = 320, max_disp: float = 64.0) -> Frame:
     """Config 1 of BASELINE.json: a single 320x240 pair, D=64."""
     return make_sequence(seed, n_frames=1, height=height, width=width, max_disp=max_disp).frames[0]
+
+
+def make_loss_case(seed: int, B: int = 1, H: int = 32, W: int = 48, iters: int = 3, empty: bool = False) -> dict:
+    """Inputs of the training objective (train_stereo.py:362-399) for one frame, float32 numpy arrays:
+    flow [B,1,H,W] (negative disparity), valid [B,H,W] (the dataset's raw map: 0 / 0.3 / 0.7 / 1, with rectangular holes; all 0
+    when `empty`), up [iters,2,B,1,H,W] and q [iters,2,B,1,H/4,W/4] (the [flow, flow_refine] pairs of every iteration), grad
+    [iters,B,2,H/4,W/4], flow_mono / flow_init [B,1,H,W], cost_volume [B,W/4,H/4,W/4].
+    The disparity is a ramp over the top half (the GT index of init_loss near 0, some below) and near 0 over the bottom half (the
+    index near D-1), with a step edge (gradients above the < 5 bound) and a few pixels beyond the |flow| < 700 bound.  The cost
+    volume is mostly negative noise with a peak at the GT index, so that the zero fill of masked candidates enters the top-k."""
+    gen = np.random.Generator(np.random.Philox(key=int(seed) + 0x10550))
+    h, w = H // 4, W // 4
+    x = np.arange(W, dtype=np.float64)[None, :]
+    disp = np.empty((B, H, W))
+    for b in range(B):
+        a = gen.uniform(0.85, 1.1)
+        top = a * x * np.ones((H // 2, 1)) + gen.normal(0, 0.3, (H // 2, W))
+        bot = np.abs(gen.normal(0.15, 0.1, (H - H // 2, W)))
+        d = np.concatenate([top, bot], 0)
+        c0 = int(gen.integers(W // 4, 3 * W // 4))
+        d[:, c0:] += gen.uniform(6, 10)                     # step edge
+        d = np.maximum(d, 0.0)
+        d[int(gen.integers(0, H)), int(gen.integers(0, W))] = 800.0     # beyond max_flow
+        disp[b] = d
+    flow = (-disp[:, None]).astype(np.float32)
+    valid = gen.choice(np.array([0.0, 0.3, 0.7, 1.0, 1.0, 1.0, 1.0, 1.0]), size=(B, H, W))
+    for b in range(B):
+        for _ in range(2):
+            y0, x0 = int(gen.integers(0, H - 6)), int(gen.integers(0, W - 6))
+            valid[b, y0:y0 + int(gen.integers(3, 9)), x0:x0 + int(gen.integers(3, 9))] = 0.0
+    valid[:, 4:12, 4:12] = np.where(valid[:, 4:12, 4:12] > 0, 1.0, 0.0)   # a block that survives the bilinear == 1 test
+    if empty:
+        valid[:] = 0.0
+    valid = valid.astype(np.float32)
+    up = np.empty((iters, 2, B, 1, H, W), np.float32)
+    q = np.empty((iters, 2, B, 1, h, w), np.float32)
+    flow_q = flow[:, :, ::4, ::4][:, :, :h, :w] / 4.0
+    for i in range(iters):
+        s = 6.0 * 0.6 ** i
+        up[i] = flow + gen.normal(0, s, up[i].shape) * gen.choice([0.1, 1.0], size=up[i].shape)
+        q[i] = flow_q + gen.normal(0, s / 4, q[i].shape)
+    grad = gen.normal(0, 0.5, (iters, B, 2, h, w)).astype(np.float32)
+    flow_mono = (flow + gen.normal(0, 3.0, flow.shape)).astype(np.float32)
+    flow_init = (flow + gen.normal(0, 1.5, flow.shape)).astype(np.float32)
+    cv = gen.normal(-0.2, 0.3, (B, w, h, w))
+    idx = np.clip(np.arange(w)[None, None, :] + flow_q[:, 0], 0, w - 1)         # [B,h,w]
+    peak = np.exp(-0.5 * (np.arange(w)[None, :, None, None] - idx[:, None]) ** 2)
+    cv = (cv + 0.9 * peak).astype(np.float32)
+    return dict(flow=flow, valid=valid, up=up, q=q.astype(np.float32), grad=grad, flow_mono=flow_mono, flow_init=flow_init,
+                cost_volume=cv)
