@@ -38,7 +38,8 @@ typedef void* tcs_stream_t;
 int tcs_abi_version(void);                 /* bumped when a signature changes (7: grouped launches, blend_warm_*; 8: `products`, the
                                               last field of tcs_conv_desc and tcs_conv_s16_desc; 9: the ordered splat entry points;
                                               10: tcs_conv2d_group_fused; 11: the *_mixed entry points;
-                                              12: tcs_convex_upsample_pair, tcs_resize_bilinear_scaled; 13: the tcs_*loss* entry points) */
+                                              12: tcs_convex_upsample_pair, tcs_resize_bilinear_scaled; 13: the tcs_*loss* entry points;
+                                              14: tcs_corr_lookup_backward, tcs_corr_build_backward*) */
 const char* tcs_error_string(int code);
 
 /* ------------------------------------------------------------------------------------------------
@@ -87,6 +88,35 @@ int tcs_corr_lookup(const float* pyr0, const float* pyr1, const float* pyr2, con
  * caller) every workgroup records the device wall clock (s_memrealtime, 100 MHz) at its start and end, so the
  * launch duration = max(end) - min(start) can be read without a profiler.  NULL in production. */
 int tcs_corr_lookup_blocks(int B, int H, int W);
+
+/*
+ * Backward of CorrBlock1D.__call__ (core/corr.py:33-52 with core/utils/utils.py:82-97): what autograd
+ * of the four F.grid_sample calls and the avg_pool2d chain (corr.py:20-23) gives for one lookup.
+ *   pyr0..pyr3, coords, radius : as passed to tcs_corr_lookup (the levels are read only for grad_coords)
+ *   grad_out    : [B, 4*(2r+1), H, W], the gradient of the lookup's output
+ *   grad_vol    : [B,H,W,W] gradient w.r.t. the natural level 0 volume V, every entry written  (nullable)
+ *                 dV[b,h,w1,w2] = sum_i 2^-i sum_t g_i[t] * lerp weight of tap w2>>i (taps outside a level: 0)
+ *   grad_coords : [B,1,H,W], sum_i 2^-i sum_t g_i[t] (v_i[t+1] - v_i[t]) (floor-based lerp)   (nullable)
+ * No atomics: two calls on the same inputs are bit-equal.
+ */
+int tcs_corr_lookup_backward(const float* pyr0, const float* pyr1, const float* pyr2, const float* pyr3,
+                             const float* coords, const float* grad_out, int B, int H, int W, int radius,
+                             float* grad_vol, float* grad_coords, tcs_stream_t stream);
+
+/* scratch needed by tcs_corr_build_backward (0 at this version: the call then accepts scratch = NULL) */
+size_t tcs_corr_build_backward_scratch_bytes(int B, int C, int H, int W);
+/*
+ * Backward of CorrBlock1D.corr (core/corr.py:54-62): autograd of the einsum and of both F.normalize
+ * calls (eps 1e-12; a pixel with |f| < eps takes d f = d n / eps, as torch does).
+ *   fmap1, fmap2 : [B,C,H,W], the inputs of the tcs_corr_build call that filled `workspace`
+ *   workspace    : that build's workspace (its inverse norms are read)
+ *   grad_vol     : [B,H,W,W] gradient w.r.t. V (the sum of every consumer's contribution)
+ *   grad_fmap1, grad_fmap2 : [B,C,H,W], written in full                                    (nullable each)
+ * Fixed reduction order, no atomics: repeated calls are bit-equal.
+ */
+int tcs_corr_build_backward(const float* fmap1, const float* fmap2, const void* workspace, const float* grad_vol,
+                            int B, int C, int H, int W, float* grad_fmap1, float* grad_fmap2, void* scratch,
+                            tcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Temporal warp                                 (core/utils/geo_utils.py, core/utils/splatting/softsplat.py)

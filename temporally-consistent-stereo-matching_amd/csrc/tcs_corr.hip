@@ -306,6 +306,225 @@ __global__ __launch_bounds__(64 * LPB) void k_corr_lookup(const float* __restric
 }
 
 // ------------------------------------------------------------------------------------------------
+// 5. lookup backward (autograd of corr.py:33-52: four grid_sample backwards + the avg-pool chain).
+//    Block = 64 consecutive pixels, 4 waves.  Staging: wave = level, lane = pixel, so the upstream
+//    gradient g[b, level*T + t, h, w] loads coalesced along w into LDS with each pixel's floor and
+//    fraction.  dV: wave k writes the whole natural row dV[p, 0..W) of pixels k, k+4, ...; lanes run
+//    along w2 (coalesced stores), every entry is written exactly once, so no memset and no atomics:
+//      dV[w2] = sum_i 2^-i * ( g_i[t] (1-fr_i) + g_i[t-1] fr_i ),  t = (w2 >> i) - j0_i,
+//    terms whose t falls outside the window (or w2 >> i >= W_i) are zero.  grad_coords (optional):
+//    lane = pixel, wave = level reads the 2r+2 skewed taps as the forward does, and
+//      dx_i = 2^-i * sum_t g_i[t] (v[t+1] - v[t]),  dcoords = ((dx_0 + dx_1) + dx_2) + dx_3.
+// ------------------------------------------------------------------------------------------------
+template <int R>
+__global__ __launch_bounds__(256) void k_corr_lookup_bwd(const float* __restrict__ pyr0, const float* __restrict__ pyr1,
+                                                         const float* __restrict__ pyr2, const float* __restrict__ pyr3,
+                                                         const float* __restrict__ coords, const float* __restrict__ gout,
+                                                         int B, int H, int W, int radius_n, float* __restrict__ gvol,
+                                                         float* __restrict__ gcoords) {
+    extern __shared__ __attribute__((aligned(16))) float lds_lb[];
+    const int radius = (R > 0) ? R : radius_n;
+    const int T = 2 * radius + 1;
+    float* s_g = lds_lb;                          // [4][T][64]
+    float* s_fr = s_g + 4 * T * 64;               // [4][64]
+    int* s_j0 = reinterpret_cast<int*>(s_fr + 4 * 64);   // [4][64]
+    float* s_dx = reinterpret_cast<float*>(s_j0 + 4 * 64);  // [4][64]
+
+    const int lane = threadIdx.x & 63;
+    const int level = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int HW = H * W;
+    const unsigned total = (unsigned)B * (unsigned)HW;
+    const unsigned p0 = blockIdx.x * 64u;
+    const unsigned p_raw = p0 + (unsigned)lane;
+    const bool active = p_raw < total;
+    const unsigned p = active ? p_raw : total - 1;
+    const int b = (int)(p / (unsigned)HW);
+    const int hw = (int)(p - (unsigned)b * (unsigned)HW);
+    const int h = hw / W, w1 = hw - h * W;
+    const int Wl = W >> level;
+
+    // the forward's coordinate arithmetic, bit for bit (k_corr_lookup)
+    float x = coords[p] * (1.0f / (float)(1 << level));
+    x = fminf(fmaxf(x, -1048576.f), 1048576.f);
+    if (!(x == x)) x = -1048576.f;
+    const float x0 = floorf(x);
+    const float fr = x - x0;
+    const int j0 = (int)x0 - radius;
+    s_fr[level * 64 + lane] = fr;
+    s_j0[level * 64 + lane] = j0;
+    const float* g = gout + ((size_t)b * 4 * T + (size_t)level * T) * HW + hw;
+    for (int t = 0; t < T; ++t) s_g[(level * T + t) * 64 + lane] = active ? g[(size_t)t * HW] : 0.f;
+
+    if (gcoords) {
+        const float* pyr_l = level == 0 ? pyr0 : (level == 1 ? pyr1 : (level == 2 ? pyr2 : pyr3));
+        const float* base = pyr_l + ((size_t)(b * H + h) * Wl) * W + w1;
+        const int q = w1 >> level;
+        float dx = 0.f, prev;
+        {
+            const int j = j0;
+            int d = q - j;
+            d = d < 0 ? d + Wl : (d >= Wl ? d - Wl : d);
+            const bool ok = j >= 0 && j < Wl;
+            const float v = base[(size_t)(ok ? d : 0) * W];
+            prev = ok ? v : 0.f;
+        }
+        for (int t = 0; t < T; ++t) {
+            const int j = j0 + t + 1;
+            int d = q - j;
+            d = d < 0 ? d + Wl : (d >= Wl ? d - Wl : d);
+            const bool ok = j >= 0 && j < Wl;
+            const float v = base[(size_t)(ok ? d : 0) * W];
+            const float nxt = ok ? v : 0.f;
+            dx = fmaf(s_g[(level * T + t) * 64 + lane], nxt - prev, dx);
+            prev = nxt;
+        }
+        s_dx[level * 64 + lane] = dx * (1.0f / (float)(1 << level));
+    }
+    __syncthreads();
+    if (gcoords && level == 0 && active)
+        gcoords[p] = ((s_dx[lane] + s_dx[64 + lane]) + s_dx[128 + lane]) + s_dx[192 + lane];
+    if (!gvol) return;
+
+    const int Wl1 = W >> 1, Wl2 = W >> 2, Wl3 = W >> 3;
+    const int rows = (int)min(64u, total - p0);
+    for (int k = level; k < rows; k += 4) {
+        float* dst = gvol + (size_t)(p0 + k) * W;
+        float fr_[4];
+        int j0_[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { fr_[i] = s_fr[i * 64 + k]; j0_[i] = s_j0[i * 64 + k]; }
+        for (int w2 = lane; w2 < W; w2 += 64) {
+            float acc = 0.f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int Wli = i == 0 ? W : (i == 1 ? Wl1 : (i == 2 ? Wl2 : Wl3));
+                const int j = w2 >> i;
+                const int t = j - j0_[i];
+                float a = 0.f, c = 0.f;
+                if (j < Wli && t >= 0 && t < T) a = s_g[(i * T + t) * 64 + k];
+                if (j < Wli && t >= 1 && t <= T) c = s_g[(i * T + t - 1) * 64 + k];
+                acc += (a * (1.f - fr_[i]) + c * fr_[i]) * (1.0f / (float)(1 << i));
+            }
+            dst[w2] = acc;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// 6. build backward, GEMM part (autograd of the einsum, corr.py:60): per image row
+//      dN1[c][w1] = sum_w2 N2[c][w2] dV[w1][w2],   dN2[c][w2] = sum_w1 N1[c][w1] dV[w1][w2],
+//    N = f * rn formed on load.  One block = 64(c) x 64(w) of one row of one map, 4 waves as 2x2
+//    tiles of 32x32, v_mfma_f32_32x32x2_f32 (exact fp32) like k_corr_gemm; K (= W) in fixed order.
+//    Results (the gradient w.r.t. the normalised map) go to the grad_fmap buffers, NCHW, stores
+//    coalesced along w; k_corr_norm_bwd then turns them into the gradient w.r.t. the raw map.
+// ------------------------------------------------------------------------------------------------
+#define GB_KC 32
+__global__ __launch_bounds__(256) void k_corr_gemm_bwd(const float* __restrict__ f1, const float* __restrict__ f2,
+                                                       const float* __restrict__ rn, const float* __restrict__ gvol,
+                                                       int B, int C, int H, int W, float* __restrict__ dn1,
+                                                       float* __restrict__ dn2, int c_blocks) {
+    __shared__ float sa[GB_KC][65];     // [k][c]
+    __shared__ float sb[GB_KC][65];     // [k][w]
+    const int w_0 = blockIdx.x * 64;
+    const int m = blockIdx.y / c_blocks;                     // 0: dN1 (K = w2), 1: dN2 (K = w1)
+    const int c_0 = (blockIdx.y - m * c_blocks) * 64;
+    const int bh = blockIdx.z, b = bh / H, h = bh % H;
+    float* out = m == 0 ? dn1 : dn2;
+    if (!out) return;                                        // block-uniform
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wr = wave >> 1, wc = wave & 1, l31 = lane & 31, half = lane >> 5;
+    const size_t HW = (size_t)H * W;
+    // operand map: the other map's features and inverse norms
+    const float* fo = (m == 0 ? f2 : f1) + (size_t)b * C * HW + (size_t)h * W;
+    const float* rno = rn + ((size_t)(m == 0 ? B : 0) + b) * HW + (size_t)h * W;
+    const float* gv = gvol + (size_t)bh * W * W;
+
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+
+    const int kk_l = tid & 31, row_l = tid >> 5;       // 8 rows x 32 k per pass
+    for (int k0 = 0; k0 < W; k0 += GB_KC) {
+        __syncthreads();
+        const int k = k0 + kk_l;
+        const bool okk = k < W;
+        const float rk = okk ? rno[k] : 0.f;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int cl = row_l + 8 * r, c = c_0 + cl;
+            sa[kk_l][cl] = (okk && c < C) ? fo[(size_t)c * HW + k] * rk : 0.f;
+        }
+        if (m == 0) {
+            // B[k=w2][w1] = dV[w1][w2]: rows w1, contiguous along k
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                const int wl = row_l + 8 * r, w = w_0 + wl;
+                sb[kk_l][wl] = (okk && w < W) ? gv[(size_t)w * W + k] : 0.f;
+            }
+        } else {
+            // B[k=w1][w2] = dV[w1][w2]: rows k, contiguous along w2
+            const int col = tid & 63, krow = tid >> 6;
+#pragma unroll
+            for (int r = 0; r < GB_KC / 4; ++r) {
+                const int kl = krow + 4 * r, kg = k0 + kl;
+                sb[kl][col] = (kg < W && w_0 + col < W) ? gv[(size_t)kg * W + w_0 + col] : 0.f;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < GB_KC; kk += 2) {
+            const float a = sa[kk + half][wr * 32 + l31];
+            const float bb = sb[kk + half][wc * 32 + l31];
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bb, acc, 0, 0, 0);
+        }
+    }
+    const int w = w_0 + wc * 32 + l31;
+    if (w >= W) return;
+    float* o = out + (size_t)b * C * HW + (size_t)h * W + w;
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+        const int c = c_0 + wr * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
+        if (c < C) o[(size_t)c * HW] = acc[reg];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// 7. build backward, F.normalize part (corr.py:58-59): with n = f rn, rn = 1 / max(|f|, 1e-12),
+//      |f| >= eps:  df = rn (dn - n sum_c n dn);      |f| < eps:  df = rn dn  (= dn / eps),
+//    as torch's autograd of x / norm(x).clamp_min(eps).  In place over dn.  Block = 64 pixels x 4
+//    channel quarters like k_inv_norm; the quarters' dot products are added in a fixed order.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_corr_norm_bwd(const float* __restrict__ f1, const float* __restrict__ f2,
+                                                       const float* __restrict__ rn, int C, int HW, float* __restrict__ g1,
+                                                       float* __restrict__ g2) {
+    __shared__ float s_part[4][64];
+    const int m = blockIdx.z;
+    float* g = m == 0 ? g1 : g2;
+    if (!g) return;                                          // block-uniform
+    const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const int p_raw = blockIdx.x * 64 + lane;
+    const int b = blockIdx.y;
+    const int p = min(p_raw, HW - 1);
+    const size_t off = (size_t)b * C * HW + p;
+    const float* f = (m == 0 ? f1 : f2) + off;
+    g += off;
+    const int cq = (C + 3) / 4, c_lo = q * cq, c_hi = min(C, (q + 1) * cq);
+    float s = 0.f;
+    for (int c = c_lo; c < c_hi; ++c) s = fmaf(f[(size_t)c * HW], g[(size_t)c * HW], s);
+    s_part[q][lane] = s;
+    __syncthreads();
+    if (p_raw >= HW) return;
+    const float r = rn[((size_t)m * gridDim.y + b) * HW + p];
+    const float t = ((s_part[0][lane] + s_part[1][lane]) + s_part[2][lane]) + s_part[3][lane];
+    // sum_c n dn = rn * sum_c f dn; the eps branch (rn = 1/eps) has no projection term
+    const float proj = (r < 1.0f / 1e-12f) ? r * t : 0.f;
+    for (int c = c_lo; c < c_hi; ++c) {
+        const float n = f[(size_t)c * HW] * r;
+        g[(size_t)c * HW] = r * (g[(size_t)c * HW] - n * proj);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
 extern "C" {
@@ -395,6 +614,53 @@ int tcs_corr_lookup(const float* pyr0, const float* pyr1, const float* pyr2, con
     else
         hipLaunchKernelGGL(k_corr_lookup<0>, dim3(g8), dim3(256), 0, tcs_stream(stream), pyr0, pyr1, pyr2, pyr3, coords, out, B, H, W,
                            radius, stamps);
+    return tcs_launch_status();
+}
+
+
+int tcs_corr_lookup_backward(const float* pyr0, const float* pyr1, const float* pyr2, const float* pyr3,
+                             const float* coords, const float* grad_out, int B, int H, int W, int radius,
+                             float* grad_vol, float* grad_coords, tcs_stream_t stream) {
+    if (!coords || !grad_out) return TCS_EINVAL;
+    if (grad_coords && (!pyr0 || !pyr1 || !pyr2 || !pyr3)) return TCS_EINVAL;
+    if (B <= 0 || H <= 0 || W < 8 || radius < 0 || radius > 16) return TCS_EINVAL;
+    if ((long long)B * H * W >= 2147483647LL) return TCS_EINVAL;
+    if (!grad_vol && !grad_coords) return TCS_OK;
+    const int T = 2 * radius + 1;
+    const size_t lds = (size_t)(4 * T * 64 + 3 * 4 * 64) * sizeof(float);
+    const int blocks = tcs_cdiv((long long)B * H * W, 64);
+    hipStream_t s = tcs_stream(stream);
+    if (radius == 4)
+        hipLaunchKernelGGL(k_corr_lookup_bwd<4>, dim3(blocks), dim3(256), lds, s, pyr0, pyr1, pyr2, pyr3, coords, grad_out,
+                           B, H, W, radius, grad_vol, grad_coords);
+    else
+        hipLaunchKernelGGL(k_corr_lookup_bwd<0>, dim3(blocks), dim3(256), lds, s, pyr0, pyr1, pyr2, pyr3, coords, grad_out,
+                           B, H, W, radius, grad_vol, grad_coords);
+    return tcs_launch_status();
+}
+
+size_t tcs_corr_build_backward_scratch_bytes(int B, int C, int H, int W) {
+    (void)B; (void)C; (void)H; (void)W;
+    return 0;          // the normalize backward runs in place over grad_fmap*: no scratch at this version
+}
+
+int tcs_corr_build_backward(const float* fmap1, const float* fmap2, const void* workspace, const float* grad_vol,
+                            int B, int C, int H, int W, float* grad_fmap1, float* grad_fmap2, void* scratch,
+                            tcs_stream_t stream) {
+    (void)scratch;
+    if (!fmap1 || !fmap2 || !workspace || !grad_vol) return TCS_EINVAL;
+    if (B <= 0 || C <= 0 || H <= 0 || W < 8) return TCS_EINVAL;
+    if ((long long)B * H > 65535) return TCS_EUNSUPPORTED;
+    if (!grad_fmap1 && !grad_fmap2) return TCS_OK;
+    hipStream_t s = tcs_stream(stream);
+    const float* rn = reinterpret_cast<const float*>(reinterpret_cast<const char*>(workspace) +
+                                                     align256((size_t)B * H * W * W * sizeof(float)));
+    const int c_blocks = tcs_cdiv(C, 64);
+    hipLaunchKernelGGL(k_corr_gemm_bwd, dim3(tcs_cdiv(W, 64), 2 * c_blocks, B * H), dim3(256), 0, s,
+                       fmap1, fmap2, rn, grad_vol, B, C, H, W, grad_fmap1, grad_fmap2, c_blocks);
+    const int HW = H * W;
+    hipLaunchKernelGGL(k_corr_norm_bwd, dim3(tcs_cdiv(HW, 64), B, 2), dim3(256), 0, s, fmap1, fmap2, rn, C, HW,
+                       grad_fmap1, grad_fmap2);
     return tcs_launch_status();
 }
 

@@ -80,6 +80,47 @@ def corr_lookup(pyr: CorrPyramid, coords: torch.Tensor, radius: int = 4, out: Op
     return out
 
 
+def corr_lookup_backward(pyr: CorrPyramid, coords: torch.Tensor, grad_out: torch.Tensor, radius: int = 4,
+                         want_vol: bool = True, want_coords: bool = False):
+    """(grad_vol [B,H,W,W] or None, grad_coords [B,1,H,W] or None) of one corr_lookup(pyr, coords, radius)."""
+    B, H, W = pyr.B, pyr.H, pyr.W
+    if tuple(coords.shape) != (B, 1, H, W):
+        raise ValueError(f"coords shape {tuple(coords.shape)} != {(B, 1, H, W)}")
+    n_ch = 4 * (2 * radius + 1)
+    if tuple(grad_out.shape) != (B, n_ch, H, W):
+        raise ValueError(f"grad_out shape {tuple(grad_out.shape)} != {(B, n_ch, H, W)}")
+    gv = _new(coords, B, H, W, W) if want_vol else None
+    gc = _new(coords, B, 1, H, W) if want_coords else None
+    rc = nv.lib().tcs_corr_lookup_backward(*[nv.ptr(t) for t in pyr.levels], nv.ptr(coords, "coords"),
+                                           nv.ptr(grad_out, "grad_out"), B, H, W, radius, nv.ptr(gv, "grad_vol"),
+                                           nv.ptr(gc, "grad_coords"), nv.stream())
+    nv.check(rc, "tcs_corr_lookup_backward")
+    return gv, gc
+
+
+def corr_build_backward(fmap1: torch.Tensor, fmap2: torch.Tensor, pyr: CorrPyramid, grad_vol: torch.Tensor,
+                        want1: bool = True, want2: bool = True):
+    """(grad_fmap1 or None, grad_fmap2 or None) of the corr_build(fmap1, fmap2) that made `pyr`, given the
+    gradient of its natural level 0 volume V [B,H,W,W]."""
+    B, Cc, H, W = _dims4(fmap1, "fmap1")
+    if tuple(fmap2.shape) != (B, Cc, H, W):
+        raise ValueError(f"fmap2 shape {tuple(fmap2.shape)} != fmap1 shape {tuple(fmap1.shape)}")
+    if (pyr.B, pyr.H, pyr.W) != (B, H, W):
+        raise ValueError("corr_build_backward: the pyramid was built from maps of another shape")
+    if tuple(grad_vol.shape) != (B, H, W, W):
+        raise ValueError(f"grad_vol shape {tuple(grad_vol.shape)} != {(B, H, W, W)}")
+    L = nv.lib()
+    g1 = _new(fmap1, B, Cc, H, W) if want1 else None
+    g2 = _new(fmap1, B, Cc, H, W) if want2 else None
+    sb = L.tcs_corr_build_backward_scratch_bytes(B, Cc, H, W)
+    scratch = torch.empty(max(sb // 4, 1), dtype=torch.float32, device=fmap1.device) if sb else None
+    rc = L.tcs_corr_build_backward(nv.ptr(fmap1, "fmap1"), nv.ptr(fmap2, "fmap2"), nv.ptr(pyr.workspace, "workspace"),
+                                   nv.ptr(grad_vol, "grad_vol"), B, Cc, H, W, nv.ptr(g1, "grad_fmap1"),
+                                   nv.ptr(g2, "grad_fmap2"), nv.ptr(scratch), nv.stream())
+    nv.check(rc, "tcs_corr_build_backward")
+    return g1, g2
+
+
 class LookupProbe:
     """Measurement hook for bench.py: hands each lookup launch its own slot of a device buffer in
     which the kernel's workgroups record the device wall clock at start/end (include/tcs_mi355.h,

@@ -205,3 +205,43 @@ def make_loss_case(seed: int, B: int = 1, H: int = 32, W: int = 48, iters: int =
     cv = (cv + 0.9 * peak).astype(np.float32)
     return dict(flow=flow, valid=valid, up=up, q=q.astype(np.float32), grad=grad, flow_mono=flow_mono, flow_init=flow_init,
                 cost_volume=cv)
+
+
+def make_corr_grad_case(seed: int, B: int = 1, C: int = 256, H: int = 3, W: int = 44, radius: int = 4, lookups: int = 3,
+                        extreme: bool = True) -> dict:
+    """Inputs of one CorrBlock1D training step (corr.py:8-79), float32 numpy arrays: fmap1, fmap2 [B,C,H,W]; coords
+    [lookups,B,1,H,W]; g_lookup [lookups,B,4(2r+1),H,W] (upstream gradients of the lookups); g_cost [B,W,H,W] (of the
+    cost volume); g_main [B,1,H,W] (of argmax_disp's main_cost).  fmap2 is fmap1 shifted by a per-row disparity plus noise, so
+    the volume has a clear winner and argmax_disp's 0.3-margin mask is mostly 1.  Pixel (0, 0, 1) of fmap1 and pixel (0, H-1, 2)
+    of fmap2 are all-zero (the F.normalize eps branch).  Coordinates: lookup 0 follows the disparity with fractional offsets,
+    lookup 1 is uniform over [-12, W+12] (taps out of range at both ends), lookup 2 is integer-valued; with `extreme`, lookup 2
+    also holds +-1000 and +-3e9 at a few pixels."""
+    gen = np.random.Generator(np.random.Philox(key=int(seed) + 0xC022))
+    T = 2 * radius + 1
+    f1 = gen.normal(0, 1, (B, C, H, W))
+    f2 = gen.normal(0, 1, (B, C, H, W))
+    disp = gen.integers(1, max(2, W // 4), size=(B, H))
+    for b in range(B):
+        for h in range(H):
+            d = int(disp[b, h])
+            f2[b, :, h, :W - d] = f1[b, :, h, d:] + gen.normal(0, 0.4, (C, W - d))
+    f1[0, :, 0, 1] = 0.0
+    f2[0, :, H - 1, 2] = 0.0
+    x = np.arange(W, dtype=np.float64)[None, None, :]
+    coords = np.empty((lookups, B, 1, H, W))
+    for k in range(lookups):
+        kind = k % 3
+        if kind == 0:
+            coords[k, :, 0] = x - disp[:, :, None] + gen.uniform(-1.5, 1.5, (B, H, W))
+        elif kind == 1:
+            coords[k, :, 0] = gen.uniform(-12, W + 12, (B, H, W))
+        else:
+            coords[k, :, 0] = np.round(gen.uniform(-6, W + 6, (B, H, W)))
+            if extreme:
+                flat = coords[k].reshape(-1)
+                flat[:4] = [1000.0, -1000.0, 3e9, -3e9]
+    g_lookup = gen.normal(0, 1, (lookups, B, 4 * T, H, W))
+    g_cost = gen.normal(0, 1, (B, W, H, W))
+    g_main = gen.normal(0, 1, (B, 1, H, W))
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)     # noqa: E731
+    return dict(fmap1=f32(f1), fmap2=f32(f2), coords=f32(coords), g_lookup=f32(g_lookup), g_cost=f32(g_cost), g_main=f32(g_main))
