@@ -5,14 +5,16 @@ Metric (BASELINE.json): stereo-pairs/sec at 640x480, D=192, 32 GRU iterations.
 A "step" is one stereo pair of a synthetic 10-frame 640x480 sequence through `TCStereo.forward`
 (frame 0 takes the argmax branch, frames 1-9 the temporal-warp branch; state resets when the clip
 wraps).  Inputs are resident in HBM before the timed region.  One process per GPU, one independent
-sequence per rank (no data-path collective; one all_gather of EPE statistics at the end).
+sequence per rank (no data-path collective; one all_gather of the timing, with --full also of EPE statistics, at the end).
 
     python bench.py --gpus N --steps K --warmup W          (N > 1 without a torchrun environment: spawns N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 with `roofline` (corr lookup: device-clock stamps of the frame's own launches, taken in a
-stamped pass after the timed region), `cpu_baseline` (the CPU oracle on the host cores, rank 0 / N=1 only) and `domain_flags`
-(the device-side NaN / saturation guard of the timed frames; non-zero = no headline, exit code 3).
+A plain run sets up, warms up, times the steps, writes --dump-outputs if given and prints ONE JSON line on rank 0 with the
+headline and `domain_flags` (the device-side NaN / saturation guard of the timed frames; non-zero = no headline, exit code 3).
+`--full` adds the passes behind the timed region: the evaluation against the synthetic ground truth, `roofline` (corr lookup:
+device-clock stamps of the frame's own launches, taken in a stamped pass), `cpu_baseline` (the CPU oracle on the host cores,
+rank 0 / N=1 only) and the extra legs (batched, prefetch, KITTI shape, TartanAir); in a plain run their fields are null.
 """
 import argparse
 import json
@@ -395,6 +397,9 @@ def main():
                     help="timed frames (default 60 = six passes over the 10-frame clip, ~1.7 s: long enough that the box's occasional slow "
                          "bursts (DESIGN.md section 6) enter the mean with their average weight instead of by luck)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the evaluation pass, the lookup roofline pass, the CPU baseline and the extra legs "
+                         "(the options below that name a leg apply only with --full); a plain run reports the headline alone")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--eager", action="store_true", help="launch kernels eagerly instead of replaying HIP graphs")
     ap.add_argument("--prefetch", action="store_true",
@@ -417,8 +422,9 @@ def main():
     ap.add_argument("--ckpt", default=os.environ.get("TCS_CKPT", "checkpoints/tartanair.pth"),
                     help="reference checkpoint (.pth with a 'model' state dict) for the TartanAir leg; weights-only load")
     ap.add_argument("--quick", action="store_true",
-                    help="A/B runs (tools/ab_bench.sh): the timed region, the domain flags and the evaluation gather only — no roofline pass, "
-                         "no CPU baseline, no extra legs")
+                    help="with --full: after the timed region, only the evaluation pass and the TartanAir leg (skipped when its files are absent) — "
+                         "no roofline pass, no CPU baseline, no batched / prefetch / KITTI legs.  Without --full it changes nothing: a plain run "
+                         "skips all of these already (the A/B scripts under tools/ still pass it and read only the timing)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher rehearsal without a GPU: ranks, rendezvous, barrier and the statistics gather only (tests)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
@@ -429,7 +435,7 @@ def main():
     if a.steps < 1:
         ap.error("--steps must be at least 1")
 
-    if a.quick:
+    if a.quick or not a.full:
         a.no_cpu_baseline, a.batched_leg, a.drop_in_steps, a.kitti_steps = True, 0, 0, 0
     a.no_prefetch = not a.prefetch
     global HEIGHT, WIDTH
@@ -490,19 +496,24 @@ def main():
     if not a.eager and (graphs is None or graphs.fell_back or any(v is None for v in graphs.cache.values())):
         raise SystemExit("bench.py: a frame ran with eager launches although HIP-graph replay was requested "
                          f"(fell_back={getattr(graphs, 'fell_back', None)}); refusing to report it as graph replay")
-    # per-rank evaluation statistics of the same clip against the synthetic ground truth, through the harness: the vector every
-    # rank contributes to the run's one collective (evaluate_stereo.py:202-220; BASELINE configs[3]'s "RCCL EPE gather")
-    from tcs_mi355.harness import reduce_stats, run_sequence
-    with torch.no_grad():
-        eval_stats = run_sequence(model, seq, iters=ITERS, device=dev)
-    domain_flags |= eval_stats.domain_flags
+    # --full: per-rank evaluation statistics of the same clip against the synthetic ground truth, through the harness: the vector
+    # every rank contributes to the run's one collective (evaluate_stereo.py:202-220; BASELINE configs[3]'s "RCCL EPE gather")
+    eval_vec = np.zeros(0, np.float64)
+    if a.full:
+        from tcs_mi355.harness import reduce_stats, run_sequence
+        log("evaluation pass over the clip")
+        with torch.no_grad():
+            eval_stats = run_sequence(model, seq, iters=ITERS, device=dev)
+        domain_flags |= eval_stats.domain_flags
+        eval_vec = eval_stats.vector()
 
     # roofline pass: the same clip with the lookup's device-clock stamps on (graphs re-captured with the stamp slots baked in)
     roof = None
     with torch.no_grad():
         try:
-            if rank != 0 or a.quick:
-                raise StopIteration                # the roofline object is rank 0's
+            if rank != 0 or a.quick or not a.full:
+                raise StopIteration                # the roofline object is rank 0's, and --full's
+            log("roofline pass: the clip with the lookup's device-clock stamps")
             probe = ops.LookupProbe(dev, slots=64)
             ops.LOOKUP_PROBE = probe
             model._pipeline().drop()
@@ -527,15 +538,15 @@ def main():
             ops.LOOKUP_PROBE = None
 
     # the run's only collective (besides the two barriers): per-rank [pairs, elapsed]; the MAX over ranks of the elapsed
-    # time and the aggregate come from it (EPE statistics ride the same vector in evaluation runs)
-    vecs = tdist.gather_vectors(np.concatenate([np.array([a.steps * S, elapsed, float(domain_flags)], np.float64), eval_stats.vector()]))
+    # time and the aggregate come from it (with --full, the EPE statistics ride the same vector)
+    vecs = tdist.gather_vectors(np.concatenate([np.array([a.steps * S, elapsed, float(domain_flags)], np.float64), eval_vec]))
     elapsed = max(float(v[1]) for v in vecs)
     total_pairs = sum(int(v[0]) for v in vecs)
     value = total_pairs / elapsed
     all_flags = 0
     for v in vecs:
         all_flags |= int(v[2])
-    gathered_eval = reduce_stats([v[3:] for v in vecs])
+    gathered_eval = reduce_stats([v[3:] for v in vecs]) if a.full else None
     if all_flags:
         log(f"S16 domain flags {all_flags:#x} on the timed frames (bit 0: an activation was clamped at 65504, bit 1: NaN / Inf): the "
             f"frames were timed on saturated tensors; refusing to print a headline")
@@ -677,7 +688,7 @@ def main():
 
     # BASELINE configs[2]: real TartanAir frames + the reference's pretrained weights, only when both are on the box
     real = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and a.full:
         real = real_data_leg(a, dev)
 
     if rank == 0:
@@ -695,8 +706,9 @@ def main():
                                   "(prefetch_leg: the same with TCStereo.prefetch after every forward)" if a.no_prefetch else
                                   "; TCStereo.prefetch(next frame) after every forward(): the next frame's image-only stage is enqueued ahead of time "
                                   "(hides its host-side launch work; on the GPU it does not overlap the loop — DESIGN.md section 6)")},
-            "domain_flags": all_flags,
-            "gathered_eval_vs_synthetic_gt": {k: (round(v, 4) if isinstance(v, float) else v) for k, v in gathered_eval.items()},
+            "full": a.full, "domain_flags": all_flags,
+            "gathered_eval_vs_synthetic_gt": (None if gathered_eval is None else
+                                              {k: (round(v, 4) if isinstance(v, float) else v) for k, v in gathered_eval.items()}),
             "roofline": roof, "cpu_baseline": cpu, "epe_vs_oracle_first_frames": epe_vs_oracle, "batched_leg": batched,
             "prefetch_leg": drop_in, "kitti_leg": kitti, "tartanair_leg": real, "dump_outputs": dumped,
             "ranks_frames": [int(v[0]) for v in vecs],

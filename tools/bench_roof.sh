@@ -6,7 +6,7 @@ for v in "$@"; do
   x=${v%%@*}; [ "$x" = "-" ] && x=""
   lib=""; [[ "$v" == *@* ]] && lib=$(pwd)/temporally-consistent-stereo-matching_amd/lib/libtcs_mi355_${v#*@}.so      # "tokens@libvariant"
   [ -n "$lib" ] && export TCS_MI355_LIB=$lib || unset TCS_MI355_LIB
-  TCS_MI355_X=$x timeout -k 10 300 python bench.py --steps 20 --no-cpu-baseline --batched-leg 0 --drop-in-steps 0 --kitti-steps 0 2>/dev/null > $out/bench_$v.json || { echo "[$v] FAILED"; exit 1; }
+  TCS_MI355_X=$x timeout -k 10 300 python bench.py --full --steps 20 --no-cpu-baseline --batched-leg 0 --drop-in-steps 0 --kitti-steps 0 2>/dev/null > $out/bench_$v.json || { echo "[$v] FAILED"; exit 1; }
   python - "$out/bench_$v.json" "$v" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]

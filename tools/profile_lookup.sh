@@ -5,15 +5,17 @@
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/$1
 mkdir -p $out
-# --quick: timed region only.  (With the stamped roofline pass behind it — graphs dropped and re-captured — the four-sequence run segfaults inside
+# --full --quick: the timed region, the evaluation pass and (when its files exist) the TartanAir leg.  (With the stamped roofline pass behind it — graphs dropped and re-captured — the four-sequence run segfaults inside
 # hipGraphLaunch UNDER rocprofv3, twice out of twice; without the profiler the same sequence is what bench.py's batched leg does every run.)
-common="--warmup 3 --quick"
+common="--warmup 3 --full --quick"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $out/p1 -- python3 $root/bench.py --steps 8 $common > $out/bench_1seq.json 2> $out/bench_1seq.err
-rocprofv3 --kernel-trace --output-format csv -d $out/p4 -- python3 $root/bench.py --steps 4 --seqs-per-gpu 4 $common > $out/bench_4seq.json 2> $out/bench_4seq.err
-rocprofv3 --kernel-trace --output-format csv -d $out/pk -- python3 $root/bench.py --steps 6 --size 375x1242 $common > $out/bench_kitti.json 2> $out/bench_kitti.err
-rocprofv3 --pmc FETCH_SIZE --kernel-include-regex k_corr_lookup --output-format csv -d $out/fetch -- python3 $root/bench.py --steps 2 --warmup 2 --no-cpu-baseline --batched-leg 0 --drop-in-steps 0 --kitti-steps 0 --eager > /dev/null 2> $out/pmc_fetch.err
-rocprofv3 --pmc WRITE_SIZE --kernel-include-regex k_corr_lookup --output-format csv -d $out/write -- python3 $root/bench.py --steps 2 --warmup 2 --no-cpu-baseline --batched-leg 0 --drop-in-steps 0 --kitti-steps 0 --eager > /dev/null 2> $out/pmc_write.err
+# each GPU run has a time limit of its own, and the first one that fails or times out ends the script: nothing runs after it
+run() { local name=$1; shift; timeout -k 10 300 "$@" > $out/$name.json 2> $out/$name.err || { echo "$name failed (rc $?)"; tail -5 $out/$name.err; exit 1; }; }
+run bench_1seq rocprofv3 --kernel-trace --output-format csv -d $out/p1 -- python3 $root/bench.py --steps 8 $common
+run bench_4seq rocprofv3 --kernel-trace --output-format csv -d $out/p4 -- python3 $root/bench.py --steps 4 --seqs-per-gpu 4 $common
+run bench_kitti rocprofv3 --kernel-trace --output-format csv -d $out/pk -- python3 $root/bench.py --steps 6 --size 375x1242 $common
+run pmc_fetch rocprofv3 --pmc FETCH_SIZE --kernel-include-regex k_corr_lookup --output-format csv -d $out/fetch -- python3 $root/bench.py --full --steps 2 --warmup 2 --no-cpu-baseline --batched-leg 0 --drop-in-steps 0 --kitti-steps 0 --eager
+run pmc_write rocprofv3 --pmc WRITE_SIZE --kernel-include-regex k_corr_lookup --output-format csv -d $out/write -- python3 $root/bench.py --full --steps 2 --warmup 2 --no-cpu-baseline --batched-leg 0 --drop-in-steps 0 --kitti-steps 0 --eager
 cd $root
 for p in p1 p4 pk; do
   trace=$(find $out/$p -name "*kernel_trace.csv" | head -1)
