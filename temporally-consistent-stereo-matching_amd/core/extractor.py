@@ -206,8 +206,7 @@ class MultiBasicEncoder(nn.Module):
 
     def can16(self, x) -> bool:
         """The all-S16 path: HIP device tensor, `none` norm, stride-1 stem."""
-        from core.update import _X
-        return bool(x.is_cuda and _hip_trunk() and self.norm_fn == "none" and self.conv1.stride == (1, 1) and "noext16" not in _X)
+        return bool(x.is_cuda and _hip_trunk() and self.norm_fn == "none" and self.conv1.stride == (1, 1))
 
     def trunk16(self, x, right=None, raw_images=False) -> "s16.S16":
         """Stem + layer1..3 on pre-split tensors (`none` norm): the stem writes S16 and every residual block stays S16.

@@ -21,7 +21,7 @@ import torch.nn as nn
 from core.corr import CorrBlock1D
 from core.extractor import BasicEncoder, MultiBasicEncoder, ResidualBlock, hip_head
 from core.update import (IN_SUM_SLOTS, BasicMultiUpdateBlock, DispGradPredictor, DispRefine, DisparityCompletor, HiddenstateUpdater,
-                         Lightfuse, _X, hip_conv)
+                         Lightfuse, hip_conv)
 from core.utils.utils import coords_grid
 from tcs_mi355 import ops, s16
 
@@ -185,16 +185,16 @@ class TCStereo(nn.Module):
     def prefetch(self, image1, image2, first=False, inputs_ready=False):
         """Optional, for callers that know the next frame (a video loop): enqueue the part of a frame that depends on nothing but its
         two images — feature / context networks, correlation pyramid, context convolutions (tc_stereo.py:101-116,147-149) — right
-        behind the frame in flight, so that its host-side launch work is done while the GPU is still busy with that frame (on this
-        stack the stage cannot run BESIDE the loop on the GPU).  The next `forward` with the SAME image tensors
+        behind the frame in flight on the caller's stream, so that its host-side launch work is done while the GPU is still busy with
+        that frame.  The next `forward` with the SAME image tensors
         (same objects, unmodified) picks the result up; any other call simply extracts again.  `first`: that frame will be called with
         params=None (start of a sequence: the arg-max prior is then built with the correlation volume) or with
         params["new_sequence"] present (a mixed batch, which always takes the arg-max).  Call it right AFTER the
-        `forward` it follows.  `inputs_ready` is kept for callers of round 3's two-stream version and no longer changes anything when
-        the stage runs on the caller's stream.  Results are identical with and without the call."""
+        `forward` it follows.  `inputs_ready` is accepted for existing callers and ignored.  Results are identical with and without
+        the call."""
         if not image1.is_cuda:
             raise RuntimeError("TCStereo.prefetch needs HIP device tensors; there is no CPU fallback")
-        self._pipeline().prefetch(image1, image2, first=bool(first), use_graph=self._graph_mode(), inputs_ready=bool(inputs_ready))
+        self._pipeline().prefetch(image1, image2, first=bool(first), use_graph=self._graph_mode())
 
     def forward(self, image1, image2, iters=12, params=None, test_mode=False, frame_id=0):
         """Disparity of a stereo pair, optionally conditioned on the previous frame (`params`):
@@ -292,7 +292,7 @@ class TCStereo(nn.Module):
                 return f1, f2, correlate(f1, f2)
 
             (fmap1, fmap2, (corr_fn, prior)), (inp_list, grad_list, net_list) = fork_join(
-                [matching_side, lambda: context(self.cnet.heads16(trunk, True, a.n_gru_layers, relu_context=True), relu_done=True)], site="frame")
+                [matching_side, lambda: context(self.cnet.heads16(trunk, True, a.n_gru_layers, relu_context=True), relu_done=True)])
         else:
             image1 = (2 * (image1 / 255.0) - 1.0).contiguous()
             image2 = (2 * (image2 / 255.0) - 1.0).contiguous()
@@ -324,12 +324,8 @@ class TCStereo(nn.Module):
                 K_scale_inv, baseline, cur_fmap=fmap1, want_fmap=False, ordered=self._hip_deterministic, start=start, prior=prior)
 
         pool = self._s16pool
-        s16_head = "dc32" not in _X
-        if s16_head:
-            disp_init, disp_mono, _, net_list = self.disp_completor.run16(pool, sparse_disp, cost, sparse_mask,
-                                                                          [c.float().contiguous() for c in net_list], tanh_nets=True)
-        else:
-            disp_init, disp_mono, _, net_list = self.disp_completor(sparse_disp, cost, sparse_mask, net_list, tanh_nets=True)
+        disp_init, disp_mono, _, net_list = self.disp_completor.run16(pool, sparse_disp, cost, sparse_mask,
+                                                                      [c.float().contiguous() for c in net_list], tanh_nets=True)
         disp_init = disp_init.float().contiguous()
 
         if last_net_list is None:
@@ -342,17 +338,14 @@ class TCStereo(nn.Module):
                 if i + 1 < len(last_net_list):
                     grid = ops.grid_halve(grid)
 
-        # previous / current hidden-state fusion (tc_stereo.py:167-168; tanh applied by the completor's last convolutions)
-        if s16_head:
-            # the three Lightfuse cells on S16 tensors, updating the completor's hidden states in place; a first frame fuses with zeros
-            for i, (h, fuse) in enumerate(zip(net_list, self.previous_current_hideen_fuse)):
-                if warped is None:
-                    x = pool.get(("frame", "zero", i), h.B, h.C, h.H, h.W, h.device)          # never written: stays zero
-                else:
-                    x = s16.to_s16(warped[i], out=pool.get(("frame", "warped", i), h.B, h.C, h.H, h.W, h.device))
-                fuse.step16(pool, h, [x])
-        else:
-            net_list = self.fuse_previous_current_hidden_state(net_list, [torch.zeros_like(x) for x in net_list] if warped is None else warped)
+        # previous / current hidden-state fusion (tc_stereo.py:167-168; tanh applied by the completor's last convolutions): the three
+        # Lightfuse cells on S16 tensors, updating the completor's hidden states in place; a first frame fuses with zeros
+        for i, (h, fuse) in enumerate(zip(net_list, self.previous_current_hideen_fuse)):
+            if warped is None:
+                x = pool.get(("frame", "zero", i), h.B, h.C, h.H, h.W, h.device)          # never written: stays zero
+            else:
+                x = s16.to_s16(warped[i], out=pool.get(("frame", "warped", i), h.B, h.C, h.H, h.W, h.device))
+            fuse.step16(pool, h, [x])
 
         coords0 = self._coords0(fmap1)
         coords1 = (coords0 - disp_init).contiguous()
@@ -369,7 +362,8 @@ class TCStereo(nn.Module):
         a = self.args
         fmap1, corr_fn = feats["fmap1"], feats["corr_fn"]
         inp_list, grad_list = feats["inp_list"], feats["grad_list"]
-        coords1, net_list = start["coords1"], start["net_list"]
+        # (hidden states: the S16 tensors the head's completor / Lightfuse cells left, updated in place by the loop)
+        coords1, nets = start["coords1"], start["net_list"]
         coords0 = self._coords0(fmap1)
         trace = getattr(self, "_trace", None)
 
@@ -377,11 +371,6 @@ class TCStereo(nn.Module):
         # feature buffer live in S16 pool buffers; 1-2 channel geometry (coords, disparity, gradients) stays fp32 ----
         pool = self._s16pool
         n3 = a.n_gru_layers == 3
-        # (hidden states: the S16 tensors the head's completor / Lightfuse cells left, updated in place by the loop; fp32 only on the
-        # A/B path of the fp32-tensor head)
-        nets = [t if isinstance(t, s16.S16) else
-                s16.to_s16(t.float().contiguous(), out=pool.get(("frame", "net", i), t.shape[0], t.shape[1], t.shape[2], t.shape[3], t.device))
-                for i, t in enumerate(net_list)]
         grads16 = [s16.to_s16(t.float().contiguous(), out=pool.get(("frame", "ctxg", i), t.shape[0], t.shape[1], t.shape[2], t.shape[3], t.device))
                    for i, t in enumerate(grad_list)]
         dg_pre = self.disp_grad_refine.prepare(pool, grads16)      # the context share of three convolutions: once per frame
@@ -415,7 +404,7 @@ class TCStereo(nn.Module):
             def coarse_branch():
                 if hu_delta is not None:
                     self.hiddenstate_update.run(pool, nets[0], hu_delta)
-                if isinstance(up32_now, tuple):          # gru32 ran ahead together with the early share of gru16
+                if up32_now is not None:                 # gru32 ran ahead together with the early share of gru16
                     return ub.gru16_late(pool, nets, up32_now[1])
                 if n3 and a.slow_fast_gru:
                     ub.run_coarse(pool, nets, inp_list, iter16=False, iter32=True, want_up16=False)
@@ -425,20 +414,20 @@ class TCStereo(nn.Module):
 
             up32_now = join(early32)                     # (None on the first iteration: gru32 then runs inside the coarse branch)
             early32 = None
-            up16, (corr, m) = fork_join([coarse_branch, enc_branch], site="iter")
+            up16, (corr, m) = fork_join([coarse_branch, enc_branch])
             if side is not None:
                 side.launch()                            # the previous iteration's mask head + pair upsampling (behind the blend)
             run_ahead = plain and trace is None and itr + 1 < iters
             # net16 is final for this iteration: gru32 of the NEXT iteration + gru16's early share (update.py) may start from here
             def ahead():
                 up32 = ub.run_gru32(pool, nets, inp_list)
-                return (up32, ub.gru16_early(pool, nets, inp_list, up32)) if "nog16split" not in _X else up32
+                return up32, ub.gru16_early(pool, nets, inp_list, up32)
             at_join = mark() if run_ahead else None                # forked HERE, enqueued behind gru08 / the flow head (never the join's first child)
             sums = getattr(self, "_checksums", None)       # debugging hook (tools/determinism_check.py): device-side sums, no sync
             lazy = trace is None and sums is None           # the hooks want the flow head's / residual head's outputs as tensors
             delta_flow = ub.run_fine(pool, nets, inp_list, m, up16, lazy=lazy)
             if at_join is not None:
-                early32 = spawn(ahead, site="gru32", after=at_join)
+                early32 = spawn(ahead, after=at_join)
             # disp_q = x - (coords1 + delta), 5 * disp2disp_gradient_xy (update.py:199) and the gradient candidates in one
             # launch (with the flow head's last convolution finished from its tap partials); coords1 is replaced by the blend
             # kernel's output below
@@ -448,8 +437,8 @@ class TCStereo(nn.Module):
                 disp_q, g5, cands = ops.flow_step_grads(coords1, delta_flow, scale=5.0)
             disp_grad, context = self.disp_grad_refine.run(pool, g5, cands, dg_pre, lazy=lazy, slot=itr if itr < IN_SUM_SLOTS else None)
             last = itr == iters - 1
-            # (not on the last iteration: no lookup follows; "nowarm": A/B)
-            warm = corr_fn._pyr if (not last and "nowarm" not in _X and a.corr_levels == 4) else None
+            # (not on the last iteration: no lookup follows)
+            warm = corr_fn._pyr if (not last and a.corr_levels == 4) else None
             if side is None:
                 refined, up_mask, fused = self.disp_refine.run(pool, disp_grad, disp_q, nets[0], context, want_mask=last, motion=motion,
                                                                warm_pyramid=warm, warm_radius=a.corr_radius)
@@ -531,7 +520,7 @@ class _OutputsSide:
             self.model.disp_refine.mask_head(self.pool, fused, out=self.mask)
             ops.convex_upsample_pair(disp_q, refined, self.mask, self.up[itr, 0], self.up[itr, 1], self.q[itr, 0], self.q[itr, 1])
 
-        self.running = spawn(side, site="outputs", slot=1, after=at)
+        self.running = spawn(side, slot=1, after=at)
 
     def join(self):
         from tcs_mi355.streams import join

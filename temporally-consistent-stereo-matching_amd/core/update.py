@@ -13,8 +13,6 @@ the refinement loop the activations stay in the convolutions' operand form ("S16
 methods take and return S16 tensors out of a per-model buffer pool, and `forward` is a thin conversion wrapper
 around `run`, so module-level parity tests exercise exactly the kernels the frame uses.
 """
-import os
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -141,13 +139,6 @@ def pool_of(module) -> s16.S16Pool:
     return p
 
 
-# A/B switches for benchmarking sessions (tools/, gpurun logs): comma-separated tokens in TCS_MI355_X.  Never set in production.
-_X = set(t for t in os.environ.get("TCS_MI355_X", "").split(",") if t)
-# Independent layer pairs as ONE grouped launch (tcs_conv2d_s16_group / tcs_conv2d_group) instead of two branches of the captured graph;
-# "nogroup" (A/B): two launches in a row.
-GROUP = "nogroup" not in _X
-
-
 def conv16(pool, conv, srcs, act="none", addend=None, post_scale=1.0, out=None, want32=False, tag="o", addend16=None, pc=None, tile_cfg=0):
     """A Conv2d on S16 sources -> S16 (a pool buffer owned by this conv, or `out`), or fp32 NCHW when want32.
     `pc`: a K-slice of the layer's weights (packed16_part) when part of its input was already accumulated into `addend`."""
@@ -189,7 +180,7 @@ def up_block16(pool, block: Conv2x_IN, x: s16.S16, rem: s16.S16, slot=None) -> s
     dc = block.conv1.conv
     y = pool.get((id(dc), "o"), x.B, dc.out_channels, 2 * x.H, 2 * x.W, x.device)
     stats = None
-    if slot is not None and "noinfuse" not in _X and s16.deconv_in_stats_ok(x.B, dc.out_channels, x.H, x.W):
+    if slot is not None and s16.deconv_in_stats_ok(x.B, dc.out_channels, x.H, x.W):
         stats = up_block_sums(pool, block, x.B, x.device)[int(slot)]
     s16.deconv4x4s2(packed_deconv(dc), [x], out16=y, in_stats=stats)
     norm = (lambda **kw: s16.instance_norm_apply(y, stats, **kw)) if stats is not None else (lambda **kw: s16.instance_norm(y, **kw))
@@ -227,37 +218,6 @@ def packed_deconv(deconv: nn.ConvTranspose2d) -> ops.PackedConv:
         hit = (key, ops.pack_deconv4x4s2(w, nprod))
         deconv._tcs_packed = hit
     return hit[1]
-
-
-def hip_up_block(block: Conv2x_IN, x, rem):
-    """Conv2x_IN(deconv=True, concat=False) (basic_layers.py:38-77) on the HIP library:
-    transposed conv -> InstanceNorm -> LeakyReLU -> (+ rem) -> 3x3 conv [-> InstanceNorm] -> LeakyReLU."""
-    y = ops.deconv4x4s2(packed_deconv(block.conv1.conv), [x.float().contiguous()])
-    if y.shape != rem.shape:
-        y = F.interpolate(ops.instance_norm(y, act="leaky"), size=rem.shape[-2:], mode="nearest") + rem
-    else:
-        y = ops.instance_norm(y, act="leaky", addend=rem.float().contiguous())
-    if block.conv2.use_in:
-        z = hip_conv(block.conv2.conv, [y])
-        return ops.instance_norm(z, act="leaky" if block.conv2.relu else "none")
-    return hip_conv(block.conv2.conv, [y], act="leaky" if block.conv2.relu else "none")
-
-
-def hip_seq(seq: nn.Sequential, srcs, last_act="none"):
-    """conv -> ReLU -> conv chains declared as nn.Sequential(conv, ReLU, conv[, ReLU|Sigmoid])."""
-    x = list(srcs)
-    mods = list(seq)
-    i = 0
-    while i < len(mods):
-        conv = mods[i]
-        act = "none"
-        if i + 1 < len(mods) and not isinstance(mods[i + 1], nn.Conv2d):
-            nxt = mods[i + 1]
-            act = {nn.ReLU: "relu", nn.LeakyReLU: "leaky", nn.Sigmoid: "sigmoid"}[type(nxt)]
-            i += 1
-        x = [hip_conv(conv, x, act=act)]
-        i += 1
-    return x[0]
 
 
 def _conv(cin, cout, k, stride=1):
@@ -345,7 +305,7 @@ class HiddenstateUpdater(_GateCell):
 
     def run(self, pool, h: s16.S16, delta: torch.Tensor) -> s16.S16:
         """One launch (tcs_hidden_update_s16): every layer is pixelwise, so a wave carries its 32 pixels through all of them."""
-        if h.C == 128 and self.convs[0].out_channels == 64 and "nohu" not in _X:
+        if h.C == 128 and self.convs[0].out_channels == 64:
             return s16.hidden_update(h, delta, *self._frags())
         x = conv32to16(pool, self.convs[0], delta, act="leaky")              # generic widths: layer by layer
         x = conv16(pool, self.convs[2], [x])
@@ -370,7 +330,7 @@ class FlowHead(nn.Module):
         """-> fp32 [B,out,H,W], or with `lazy` the tap partials of conv2 (s16.Taps) for a consumer that finishes the sum itself.
         conv2 (256 -> 1 or 2 channels, 3x3) never runs as a launch: conv1's epilogue leaves 9 partial sums per 32-channel tile and
         output (csrc/tcs_stencil.hip, "Tap partials"), and the 256-channel intermediate is never stored."""
-        if self.conv2.out_channels <= 2 and "notaps" not in _X:
+        if self.conv2.out_channels <= 2:
             taps = tap_partials(pool, self.conv1, self.conv2, [x])
             return taps if lazy else s16.taps_sum(taps)
         y = conv16(pool, self.conv1, [x], act="relu")
@@ -411,7 +371,7 @@ class BasicMotionEncoder(nn.Module):
         # convc2 | convf2 (two independent 3x3 64 -> 64 layers) as ONE grouped launch (tcs_conv2d_s16_group) instead of two graph branches
         c1 = conv32to16(pool, self.convc1, corr, act="relu")
         f1 = conv32to16(pool, self.convf1, flow, act="relu")
-        with s16.grouped(enabled=GROUP):
+        with s16.grouped():
             c = conv16(pool, self.convc2, [c1], act="relu")
             f = conv16(pool, self.convf2, [f1], act="relu")
         return conv16(pool, self.conv, [c, f], act="relu", out=motion)
@@ -547,7 +507,7 @@ class BasicMultiUpdateBlock(nn.Module):
             return None
         # the coarse GRUs first (the longer chain stays in the launch list, tcs_mi355/streams.py), the motion encoder beside them
         up16, m = fork_join([lambda: self.run_coarse(pool, net, inp, iter16, iter32),
-                             lambda: self.encoder.run(pool, flow, corr, motion)], site="coarse")
+                             lambda: self.encoder.run(pool, flow, corr, motion)])
         return self.run_fine(pool, net, inp, m, up16, update)
 
 
@@ -626,10 +586,10 @@ class DispGradPredictor(nn.Module):
         gs, cs = self.conv_grad_stem, self.conv_grad_candidate_stem
         # the two stems (update.py:200-205) layer by layer as grouped launches: [2 -> 32 | 32 -> 64] on the fp32-MFMA kernel (the candidates are
         # unbounded; the gradient stem rides the same instance), then [32 -> 32 | 64 -> 64] on S16 — no fork, no join
-        with ops.grouped(enabled=GROUP):
+        with ops.grouped():
             g1 = conv32to16(pool, gs[0], g5, act="relu")
             c1 = conv32to16(pool, cs[0], cands, act="relu")
-        with s16.grouped(enabled=GROUP):
+        with s16.grouped():
             x4_grad = conv16(pool, gs[2], [g1])
             x4_cand = conv16(pool, cs[2], [c1])
         x4 = feat(self.conv_4_4[0], [x4_grad, x4_cand], pre[0])
@@ -640,27 +600,13 @@ class DispGradPredictor(nn.Module):
         x8_up = up_block16(pool, self.conv_16_8, x16, x8, slot=slot)
         x4_up = up_block16(pool, self.conv_8_4, x8_up, x4, slot=slot)
 
+        # residual_head[0] and conv_out[0] read the same x4_up (update.py:212-214): one 64 -> 128 + 64 launch whose epilogue
+        # sends the two channel ranges their own ways, and residual_head[2] (128 -> 2) is folded into that epilogue as tap partials:
+        # the 128-channel hidden tensor is never stored; (5*grad + residual) / 5 (update.py:213) is finished by the consumer
         rh0, co0 = self.residual_head[0], self.conv_out[0]
-        if "noheadfuse" not in _X and rh0.out_channels % 32 == 0:
-            # residual_head[0] and conv_out[0] read the same x4_up (update.py:212-214): one 64 -> 128 + 64 launch whose epilogue
-            # sends the two channel ranges their own ways — one launch and a fork / join less per iteration
-            ctx = pool.get((id(co0), "o"), x4_up.B, co0.out_channels, x4_up.H, x4_up.W, x4_up.device)
-            if "notaps" not in _X:
-                # ... and residual_head[2] (128 -> 2) is folded into that epilogue as tap partials: the 128-channel hidden tensor is
-                # never stored; (5*grad + residual) / 5 (update.py:213) is finished by the consumer
-                taps = tap_partials(pool, rh0, self.residual_head[2], [x4_up], pc=packed16_cat([rh0, co0]), out16b=ctx)
-                return ((taps, g5, 0.2) if lazy else s16.taps_sum(taps, addend=g5, scale=0.2)), ctx
-            h = pool.get((id(rh0), "o"), x4_up.B, rh0.out_channels, x4_up.H, x4_up.W, x4_up.device)
-            s16.conv2d(packed16_cat([rh0, co0]), [x4_up], act="relu", out16=h, out16b=ctx, out16_split=rh0.out_channels)
-            # (5*grad + residual) / 5 (update.py:213) in the epilogue of the last conv: addend = 5*grad, scale = 1/5
-            return conv16(pool, self.residual_head[2], [h], addend=g5, post_scale=0.2, want32=True), ctx
-
-        def head():
-            h = conv16(pool, rh0, [x4_up], act="relu")
-            return conv16(pool, self.residual_head[2], [h], addend=g5, post_scale=0.2, want32=True)
-
-        grad, ctx = fork_join([head, lambda: conv16(pool, co0, [x4_up], act="relu")], site="heads")
-        return grad, ctx
+        ctx = pool.get((id(co0), "o"), x4_up.B, co0.out_channels, x4_up.H, x4_up.W, x4_up.device)
+        taps = tap_partials(pool, rh0, self.residual_head[2], [x4_up], pc=packed16_cat([rh0, co0]), out16b=ctx)
+        return ((taps, g5, 0.2) if lazy else s16.taps_sum(taps, addend=g5, scale=0.2)), ctx
 
 
 class DispRefine(nn.Module):
@@ -718,10 +664,10 @@ class DispRefine(nn.Module):
         # context_compress (3x3, 192 -> 96 -> 96) beside disp_f_stem (1x1, 27 -> 96 -> 96), layer by layer as grouped launches
         # (the 3x3 halves on the 4-row single-stage tile: a grouped launch allocates the larger LDS size of its two instances)
         t3 = 101411 if context_disp.H * context_disp.W >= 10000 else 0
-        with s16.grouped(enabled=GROUP):
+        with s16.grouped():
             c = conv16(pool, cc[0], [context_disp, context_grad], act="relu", tile_cfg=t3)
             d = conv16(pool, ds[0], [f27], act="relu")
-        with s16.grouped(enabled=GROUP):
+        with s16.grouped():
             context = conv16(pool, cc[2], [c], tile_cfg=t3)
             disp_f = conv16(pool, ds[2], [d])
         fused = conv16(pool, self.conv_fuse[0], [disp_f, context], act="relu")
@@ -730,14 +676,10 @@ class DispRefine(nn.Module):
         fused = conv16(pool, self.conv_fuse[2], [fused], act="relu")
         w = conv16(pool, self.w_head[0], [fused], act="relu")
         coords1, flow_x = torch.empty_like(disp), torch.empty_like(disp)
-        if "noblendfuse" not in _X:
-            # the blend runs as the epilogue of w_head's 1x1 convolution: one launch less on the iteration's critical chain
-            # `warm_pyramid` (the frame's correlation pyramid): the blend also touches the rows the next iteration's lookup reads
-            refined, delta = s16.conv1x1_blend(packed16(self.w_head[2]), [w], cand9, disp, coords1, flow_x, flow_x_s16=motion,
-                                               flow_x_channel=127, warm_pyramid=warm_pyramid, warm_radius=warm_radius)
-        else:
-            logits = conv16(pool, self.w_head[2], [w], want32=True)
-            refined, delta = s16.softmax_blend(logits, cand9, disp, coords1, flow_x, flow_x_s16=motion, flow_x_channel=127)
+        # the blend runs as the epilogue of w_head's 1x1 convolution: one launch less on the iteration's critical chain
+        # `warm_pyramid` (the frame's correlation pyramid): the blend also touches the rows the next iteration's lookup reads
+        refined, delta = s16.conv1x1_blend(packed16(self.w_head[2]), [w], cand9, disp, coords1, flow_x, flow_x_s16=motion,
+                                           flow_x_channel=127, warm_pyramid=warm_pyramid, warm_radius=warm_radius)
         mask = self.mask_head(pool, fused) if want_mask else None
         return refined, mask, dict(delta_disp=delta, coords1=coords1, flow_x=flow_x, fused=fused)
 
@@ -767,28 +709,6 @@ class DisparityCompletor(nn.Module):
         self.conv_out16_disp = cin_block(192, 192, 128)
         self.conv_out8_disp = cin_block(192, 192, 128)
         self.conv_out4_disp = cin_block(192, 192, 128)
-
-    def _cin(self, seq, srcs, act="none"):
-        """conv -> InstanceNorm -> ReLU -> conv blocks (update.py:325-367)."""
-        return hip_conv(seq[3], [ops.instance_norm(hip_conv(seq[0], srcs), act="relu")], act=act)
-
-    def _forward_hip(self, disp, cost, mask, ctx, tanh_nets=False):
-        d = (disp / 10).float().contiguous()
-        stems = [hip_seq(self.conv_disp_stem, [d]), hip_seq(self.conv_cost_stem, [cost.float().contiguous()]),
-                 hip_seq(self.conv_mask_stem, [(mask - 0.5).float().contiguous()])]
-        x4_disp = hip_seq(self.conv_disp_fuse, stems)
-        x4 = self._cin(self.conv_4_4, [x4_disp, ctx[0]])
-        x8 = self._cin(self.conv_8_8, [self._cin(self.conv_4_8, [x4]), ctx[1]])
-        x16_out = self._cin(self.conv_16_16, [self._cin(self.conv_8_16, [x8]), ctx[2]])
-        x8_out = hip_up_block(self.conv_16_8, x16_out, x8)
-        x4_out = hip_up_block(self.conv_8_4, x8_out, x4)
-        disp_mono = hip_seq(self.disp_head, [x4_out])
-        w = hip_conv(self.w_head[2], [hip_conv(self.w_head[0], [x4_out], act="relu")], act="sigmoid")
-        completed = (w * d + (1 - w) * disp_mono) * 10
-        na = "tanh" if tanh_nets else "none"                # the caller's torch.tanh (tc_stereo.py:167) in the last convolutions' epilogues
-        nets = [self._cin(self.conv_out4_disp, [x4_out, ctx[0]], na), self._cin(self.conv_out8_disp, [x8_out, ctx[1]], na),
-                self._cin(self.conv_out16_disp, [x16_out, ctx[2]], na)]
-        return completed, disp_mono * 10, w, nets
 
     def run16(self, pool, disp, cost, mask, ctx, tanh_nets=False):
         """The block on pre-split (S16) tensors — the loop's kernels (tcs_conv2d_s16, S16 InstanceNorm, the up-blocks of the gradient
@@ -824,7 +744,5 @@ class DisparityCompletor(nn.Module):
         TCStereo.forward applies to them next (tc_stereo.py:167)."""
         if not disp.is_cuda:
             raise RuntimeError("DisparityCompletor: CPU tensor (the hot path has no CPU fallback)")
-        if "dc32" in _X:                                    # A/B: round 2's fp32-tensor kernels
-            return self._forward_hip(disp, cost, mask, [c.float().contiguous() for c in context_list], tanh_nets)
         completed, mono, w, nets = self.run16(pool_of(self), disp, cost, mask, [c.float().contiguous() for c in context_list], tanh_nets)
         return completed, mono, w, [n.float() for n in nets]

@@ -65,7 +65,7 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs& a, const int bid,
     {                                                                                                   \
         _Pragma("unroll") for (int j = 0; j < IN_PT; ++j) {                                             \
             const int g = (C0) + sub + j * R;                                                           \
-            /* unconditional load from a clamped (valid) address; zero-selected in TCS_STORE_CHUNK, so nothing waits \
+            /* unconditional load from a clamped (valid) address; zero-selected in TCS_LDS_PUT_CHUNK, so nothing waits \
                for the value before the MFMA phase */                                                   \
             in_reg[j] = conv_src_ptr(a, b, min(g, a.Cin - 1), HW)[pixoff];                              \
         }                                                                                               \
@@ -75,7 +75,7 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs& a, const int bid,
             w_reg[j] = *reinterpret_cast<const f32x4*>(wsrc + ((size_t)(C0) * TAPS + row) * a.CoutPad + q * 4); \
         }                                                                                               \
     }
-#define TCS_STORE_CHUNK(C0)                                                                             \
+#define TCS_LDS_PUT_CHUNK(C0)                                                                             \
     {                                                                                                   \
         _Pragma("unroll") for (int j = 0; j < IN_PT; ++j)                                               \
             if (in_active && sub + j * R < KC)                                                          \
@@ -89,7 +89,7 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs& a, const int bid,
     // ---- K loop: global loads of chunk i+1 are in flight while the matrix cores work on chunk i ----
     const int cin_loop = (a.Cin + KC - 1) / KC * KC;
     TCS_LOAD_CHUNK(0)
-    TCS_STORE_CHUNK(0)
+    TCS_LDS_PUT_CHUNK(0)
     __syncthreads();
     for (int c0 = 0; c0 < cin_loop; c0 += KC) {
         const bool has_next = c0 + KC < cin_loop;
@@ -111,13 +111,13 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs& a, const int bid,
         }
         if (has_next) {
             __syncthreads();            // every wave has finished reading this chunk
-            TCS_STORE_CHUNK(c0 + KC)    // (waits here for the prefetched registers)
+            TCS_LDS_PUT_CHUNK(c0 + KC)    // (waits here for the prefetched registers)
             __syncthreads();
         }
     }
 
 #undef TCS_LOAD_CHUNK
-#undef TCS_STORE_CHUNK
+#undef TCS_LDS_PUT_CHUNK
 
     // ---- epilogue ----
     const int px = x0 + l31, py = y0 + wave;

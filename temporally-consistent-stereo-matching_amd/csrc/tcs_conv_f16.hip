@@ -19,12 +19,6 @@
 // so staging weights is a straight 16-byte-per-lane copy; activations are split on the fly.
 #include "tcs_conv_common.h"
 
-#ifdef TCS_CONV_STAMPS
-// Diagnostic build only (lib/libtcs_mi355_stamps.so): per-phase shader-clock sums of the K loop, per wave.
-__device__ unsigned long long tcs_conv_stamps[8 * 16384];
-#define TCS_STAMP(T) { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(T) :: "memory"); }
-#endif
-
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
 
@@ -52,7 +46,7 @@ __device__ __forceinline__ void split_f16x2(float x0, float x1, half2_t& hi, hal
 // owns patch row(s) `row`.
 // A wave issues one instruction every ~4-5 cycles, and a chunk costs ~700 non-MFMA instructions per block (loads,
 // fp16 split, LDS traffic) against 27*MT*MP MFMAs per wave: with 4 waves the block is issue-bound at 4-5x the MFMA time
-// (measured with in-kernel stamps, tools/conv_phases.py).
+// (measured with in-kernel stamps of a diagnostic build, since retired).
 // ROWS = waves along the patch rows (patch = ROWS*MP rows): 5 instead of 4 turns the 600- and 300-workgroup grids of the
 // 1/4-scale layers (2.3 and 1.2 workgroups per CU: some CUs carry one more than the others for the whole kernel) into
 // 480 and 240 (at most 2 / 1 per CU).
@@ -146,7 +140,7 @@ __device__ __forceinline__ void f16_conv_body(const ConvArgs& a) {
             const int g0 = (C0) + (part * GPT + gi) * 8;                  /* wave-uniform */                \
             if (a.src_align8) {                                                                             \
                 /* one scalar base pointer per group; loads are unconditional on clamped (valid) addresses and \
-                   zero-selected in TCS_STORE_CHUNK, so nothing waits for them before the MFMA phase */      \
+                   zero-selected in TCS_LDS_PUT_CHUNK, so nothing waits for them before the MFMA phase */      \
                 gptr_t bj = nbase[gi];                                    /* scalar; +HWi per channel */    \
                 _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                             \
                     _Pragma("unroll") for (int k = 0; k < PPT; ++k)                                         \
@@ -162,7 +156,7 @@ __device__ __forceinline__ void f16_conv_body(const ConvArgs& a) {
             }                                                                                               \
         }                                                                                                   \
     }
-#define TCS_STORE_CHUNK(in_reg, w_reg, C0)                                                                                 \
+#define TCS_LDS_PUT_CHUNK(in_reg, w_reg, C0)                                                                                 \
     {                                                                                                       \
         _Pragma("unroll") for (int k = 0; k < PPT; ++k) {                                                   \
             if (s_pix[k] > -2) {                                                                            \
@@ -279,59 +273,23 @@ __device__ __forceinline__ void f16_conv_body(const ConvArgs& a) {
     TCS_GROUP_BASES(0)
     TCS_LOAD_CHUNK(in_regA, w_regA, 0)
     TCS_GROUP_BASES(KC)
-    TCS_STORE_CHUNK(in_regA, w_regA, 0)
+    TCS_LDS_PUT_CHUNK(in_regA, w_regA, 0)
     __syncthreads();
     {
         // global loads of chunk i+1 are in flight during the MFMAs of chunk i
-#ifdef TCS_CONV_STAMPS
-        unsigned long long ts0, ts1, ts2, ts3, ts4, ts5, acc_t[5] = {0, 0, 0, 0, 0};
-#endif
         for (int i = 0; i < nchunks; ++i) {
             const bool has_next = i + 1 < nchunks;
-#ifdef TCS_CONV_STAMPS
-            TCS_STAMP(ts0)
-#endif
-            // TCS_ABLATE_* are diagnostic builds (tools/conv_ablate.sh): results are wrong, only the timing is of interest
-#ifndef TCS_ABLATE_LOAD
             if (has_next) {
                 TCS_LOAD_CHUNK(in_regA, w_regA, (i + 1) * KC)
                 TCS_GROUP_BASES((i + 2) * KC)
             }
-#endif
-#ifdef TCS_CONV_STAMPS
-            TCS_STAMP(ts1)
-#endif
-#ifndef TCS_ABLATE_MMA
             TCS_COMPUTE()
-#endif
-#ifdef TCS_CONV_STAMPS
-            TCS_STAMP(ts2)
-#endif
             if (has_next) {
                 __syncthreads();
-#ifdef TCS_CONV_STAMPS
-                TCS_STAMP(ts3)
-#endif
-#ifndef TCS_ABLATE_STORE
-                TCS_STORE_CHUNK(in_regA, w_regA, (i + 1) * KC)
-#endif
-#ifdef TCS_CONV_STAMPS
-                TCS_STAMP(ts4)
-#endif
+                TCS_LDS_PUT_CHUNK(in_regA, w_regA, (i + 1) * KC)
                 __syncthreads();
-#ifdef TCS_CONV_STAMPS
-                TCS_STAMP(ts5)
-                acc_t[0] += ts1 - ts0; acc_t[1] += ts2 - ts1; acc_t[2] += ts3 - ts2; acc_t[3] += ts4 - ts3; acc_t[4] += ts5 - ts4;
-#endif
             }
         }
-#ifdef TCS_CONV_STAMPS
-        if (lane == 0) {
-            const size_t w_ = ((size_t)blockIdx.x * ROWS + wave_all) % 16384;
-            for (int q = 0; q < 5; ++q) tcs_conv_stamps[w_ * 8 + q] = acc_t[q];
-            tcs_conv_stamps[w_ * 8 + 5] = nchunks;
-        }
-#endif
     }
 #undef TCS_COMPUTE
 #undef TCS_COMPUTE_ASM
@@ -341,7 +299,7 @@ __device__ __forceinline__ void f16_conv_body(const ConvArgs& a) {
 #undef TCS_WAIT_LGKM
 #undef TCS_LOAD_CHUNK
 #undef TCS_GROUP_BASES
-#undef TCS_STORE_CHUNK
+#undef TCS_LDS_PUT_CHUNK
 #undef TCS_FETCH
 #undef TCS_MMA
 
@@ -372,7 +330,7 @@ __global__ __launch_bounds__(64 * ROWS) void k_conv_f16x1(ConvArgs a) {
 // Wave-specialised variant: 4 consumer waves (MFMA only) + NP producer waves (global loads, fp16 split, LDS stores) per
 // block, two LDS buffers, ONE barrier per chunk.  In k_conv_f16x3 every wave does all of a chunk's work in sequence
 // (issue loads -> MFMAs -> wait loads -> split + store -> barriers), ~3,000 cycles per chunk of which 864*MT are MFMA
-// (in-kernel stamps and phase-ablated builds, tools/conv_phases.py / tools/conv_ablate.sh): co-resident blocks run those
+// (in-kernel stamps and phase-ablated diagnostic builds, since retired): co-resident blocks run those
 // phases in lock step, so the phases add instead of overlapping.  Here the staging of chunk i+1 runs on other waves of
 // the same SIMDs while chunk i is multiplied, and a chunk costs max(MFMA, staging) instead of their sum.
 // Same tiling, LDS images and packed weights as k_conv_f16x3<KS, MT, 1, KSTEPS, EPI>; stride 1 only.
@@ -455,7 +413,7 @@ __device__ __forceinline__ void f16_conv_ws_body(const ConvArgs& a) {
             }                                                                                               \
         }                                                                                                   \
     }
-#define WS_STORE(BUF, C0)                                                                                   \
+#define WS_LDS_PUT(BUF, C0)                                                                                   \
     {                                                                                                       \
         unsigned char* s_in_hi = lds8 + (BUF) * BUF_BYTES;                                                  \
         unsigned char* s_in_lo = s_in_hi + IN_BYTES;                                                        \
@@ -488,7 +446,7 @@ __device__ __forceinline__ void f16_conv_ws_body(const ConvArgs& a) {
         WS_GROUP_BASES(0)
         WS_LOAD(0)
         WS_GROUP_BASES(KC)
-        WS_STORE(0, 0)
+        WS_LDS_PUT(0, 0)
         if (nchunks > 1) {
             WS_LOAD(KC)
             WS_GROUP_BASES(2 * KC)
@@ -496,7 +454,7 @@ __device__ __forceinline__ void f16_conv_ws_body(const ConvArgs& a) {
         __syncthreads();                                          // chunk 0 is in buffer 0
         for (int i = 0; i < nchunks; ++i) {
             if (i + 1 < nchunks) {
-                WS_STORE((i + 1) & 1, (i + 1) * KC)               // buffer (i+1)&1 was last read in iteration i-1
+                WS_LDS_PUT((i + 1) & 1, (i + 1) * KC)               // buffer (i+1)&1 was last read in iteration i-1
                 if (i + 2 < nchunks) {
                     WS_LOAD((i + 2) * KC)
                     WS_GROUP_BASES((i + 3) * KC)
@@ -506,7 +464,7 @@ __device__ __forceinline__ void f16_conv_ws_body(const ConvArgs& a) {
         }
 #undef WS_GROUP_BASES
 #undef WS_LOAD
-#undef WS_STORE
+#undef WS_LDS_PUT
         return;
     }
 
@@ -853,12 +811,6 @@ __global__ __launch_bounds__(64 * C1_WAVES) void k_conv3x3_cout1(const float* __
         out[(size_t)b * HW + (size_t)y * W + col] = r;
     }
 }
-
-#ifdef TCS_CONV_STAMPS
-extern "C" int tcs_debug_read_conv_stamps(unsigned long long* host_out, int n_waves) {
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(tcs_conv_stamps), (size_t)n_waves * 8 * sizeof(unsigned long long)) == hipSuccess ? 0 : -2;
-}
-#endif
 
 extern "C" {
 

@@ -67,8 +67,6 @@ struct S16Args {
     const float* tap_w; float* tap_out; int tap_nout, tap_ntile;   // LINEAR: tap partials of a following 3x3 conv to 1-2 channels (tcs_stencil.hip)
     float tap_unscale;
     const float* warm_pyr0; const float* warm_pyr1; const float* warm_pyr2; const float* warm_pyr3; int warm_radius;   // BLEND9: see tcs_mi355.h
-    int ablate;                         // diagnostic builds only (-DTCS_S16_ABLATE, tools/conv_s16_ablate.py): bit 0 skip the
-                                        // input DMA, bit 1 skip the weight DMA, bit 2 skip operand reads + MFMAs (timing only)
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -84,17 +82,6 @@ template <int EPI, bool TP = false>
 __device__ __forceinline__ void s16_epilogue_tile(const S16Args& a, int b, int co0, int py, int px, const f32x16& acc, bool st = true) {
     const int H = a.H, W = a.W;
     const size_t HW = (size_t)H * W, pix = (size_t)py * W + px;
-#ifdef TCS_S16_PROBE_SLIM
-    // diagnostic build (tools/conv_s16_probe.sh): a one-store epilogue, so that the register allocation — and with it the number of waves
-    // per SIMD — is the K loop's own.  Results are wrong by construction; only the timing of LINEAR launches means anything.
-    if (EPI == TCS_EPI_LINEAR && a.out32) {
-        float t = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) t += acc[r];
-        if (st) a.out32[((size_t)b * a.out_ctot + a.out_coff + min(co0, a.Cout - 1)) * HW + pix] = t;
-        return;
-    }
-#endif
     const int Hp = H + 2, Wp = W + 2;
     // tap partials: this tile's four weight fragments (k-steps 2*tile, 2*tile + 1; hi, lo) are requested first, used last
     const bool taps_here = TP && EPI == TCS_EPI_LINEAR && (co0 >> 5) < a.tap_ntile;
@@ -445,22 +432,10 @@ __device__ __forceinline__ const char* uniform_ptr(const char* p) {
     return reinterpret_cast<const char*>(((unsigned long long)hi << 32) | lo);
 }
 
-#ifdef TCS_S16_ABLATE
-#define S16_ABL_DMA(IS_INPUT) (!(a.ablate & ((IS_INPUT) ? 1 : 2)))
-#define S16_ABL_COMPUTE (!(a.ablate & 4))
-// per-workgroup phase stamps of the diagnostic build (100 MHz device clock): [start, first stage landed, K loop done, end]
-__device__ unsigned long long tcs_s16_stamps[4 * 8192];
-#define S16_STAMP(I) { if (threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.x < 8192) tcs_s16_stamps[4 * blockIdx.x + (I)] = __builtin_amdgcn_s_memrealtime(); }
-#else
-#define S16_STAMP(I) {}
-#define S16_ABL_DMA(IS_INPUT) true
-#define S16_ABL_COMPUTE true
-#endif
-
 // RPW ("rows per wave") = 2: a wave owns TWO output rows, i.e. every weight fragment it fetches feeds two activation fragments (6 operand
 // fragments per 6 MFMAs instead of 8).  The block is ROWS / RPW waves; LDS per block is unchanged.  A tile OPTION (cfg 12xxxx), not the
 // heuristic's choice: it only beat the one-row tile while that one was starved of occupancy (see s16_epilogue_tile's TP); with a
-// one-store epilogue (-DTCS_S16_PROBE_SLIM) every tile shape times within 5 % — DESIGN.md section 4.
+// one-store epilogue (a diagnostic build, since retired) every tile shape times within 5 % — DESIGN.md section 4.
 //
 // Occupancy target (second __launch_bounds__ argument of hipcc = minimum waves per SIMD).  The K loop of a one-row 32-channel tile needs
 // 59 VGPRs; what the kernel is allocated is its epilogue's appetite, and the allocator lands a few registers above a step of the
@@ -470,9 +445,6 @@ __device__ unsigned long long tcs_s16_stamps[4 * 8192];
 constexpr int s16_min_waves(int MT, int EPI, int RPW, bool TP) {
     // (two-row tiles: the K loop needs ~100 registers, prologue and epilogue take 182-212; forcing 128 makes the epilogue spill 54-108
     // registers to scratch and costs 50 % of the kernel: 128 -> 128 43.5 against 29.3 us)
-#ifdef TCS_S16_PROBE_SLIM
-    if (EPI == TCS_EPI_LINEAR && !TP) return RPW == 2 ? (MT == 2 ? 3 : 4) : (MT == 2 ? 4 : 8);
-#endif
     if (RPW != 1 || MT != 1) return 1;
     if (TP || EPI == TCS_EPI_GRU_Q) return 4;
     if (EPI == TCS_EPI_LINEAR) return 5;
@@ -508,7 +480,6 @@ __device__ __forceinline__ void s16_conv_body(const S16Args& a, const int bid_, 
     static_assert(R <= 15, "lgkmcnt field");
     static_assert(STAGE_BYTES <= 65536, "ds_read immediate offsets are 16 bits");
 
-    S16_STAMP(0)
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, half = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int ct, patch;
@@ -565,7 +536,7 @@ __device__ __forceinline__ void s16_conv_body(const S16Args& a, const int bid_, 
         _Pragma("unroll") for (int j = 0; j < PPW; ++j) {                                                             \
             const int p_ = min(wave + j * NW, NP - 1);                                                                \
             const char* base_ = p_ < NPI ? in_ptr_ : w_ptr_;                                                          \
-            if (S16_ABL_DMA(p_ < NPI)) S16_DMA(voff[j], dst0_ + (unsigned)p_ * 1024u, base_)                          \
+            S16_DMA(voff[j], dst0_ + (unsigned)p_ * 1024u, base_)                                                     \
         }                                                                                                             \
     }
 
@@ -620,23 +591,20 @@ __device__ __forceinline__ void s16_conv_body(const S16Args& a, const int bid_, 
         else if (newer == 1) { asm volatile("s_waitcnt vmcnt(%0)" :: "i"(PPW) : "memory"); }
         else { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
         __builtin_amdgcn_s_barrier();                               // everyone's pieces landed; everyone is done with stage s-1
-        if (s == 0) { S16_STAMP(1) }
         if (NSTAGE >= 2 && s >= 1 && s + NSTAGE - 1 < nstage_total) {   // refill the buffer that stage s-1 was multiplied from
             const int nb = buf == 0 ? NSTAGE - 1 : buf - 1;
             S16_ISSUE(nb, s + NSTAGE - 1)
         }
-        if (S16_ABL_COMPUTE) {
-            const unsigned addr_b = addr_b0 + (unsigned)buf * STAGE_BYTES, addr_a = addr_a0 + (unsigned)buf * STAGE_BYTES;
-            Frag f0, f1;
-            S16_FETCH(f0, 0)
+        const unsigned addr_b = addr_b0 + (unsigned)buf * STAGE_BYTES, addr_a = addr_a0 + (unsigned)buf * STAGE_BYTES;
+        Frag f0, f1;
+        S16_FETCH(f0, 0)
 #pragma unroll
-            for (int i = 0; i < NSTEP; i += 2) {
-                if (i + 1 < NSTEP) { S16_FETCH(f1, (i + 1 < NSTEP ? i + 1 : 0)) S16_WAIT_LGKM(R) } else S16_WAIT_LGKM(0)
-                S16_MMA(f0)
-                if (i + 1 < NSTEP) {
-                    if (i + 2 < NSTEP) { S16_FETCH(f0, (i + 2 < NSTEP ? i + 2 : 0)) S16_WAIT_LGKM(R) } else S16_WAIT_LGKM(0)
-                    S16_MMA(f1)
-                }
+        for (int i = 0; i < NSTEP; i += 2) {
+            if (i + 1 < NSTEP) { S16_FETCH(f1, (i + 1 < NSTEP ? i + 1 : 0)) S16_WAIT_LGKM(R) } else S16_WAIT_LGKM(0)
+            S16_MMA(f0)
+            if (i + 1 < NSTEP) {
+                if (i + 2 < NSTEP) { S16_FETCH(f0, (i + 2 < NSTEP ? i + 2 : 0)) S16_WAIT_LGKM(R) } else S16_WAIT_LGKM(0)
+                S16_MMA(f1)
             }
         }
         if (NSTAGE == 1 && s + 1 < nstage_total) {
@@ -650,7 +618,6 @@ __device__ __forceinline__ void s16_conv_body(const S16Args& a, const int bid_, 
 #undef S16_ISSUE
 #undef S16_FETCH
 #undef S16_MMA
-    S16_STAMP(2)
 
     const int px = x0 + l31, py = y0 + wave * RPW;
     if constexpr (EPI == TCS_EPI_DECONV2X) {
@@ -674,10 +641,6 @@ __device__ __forceinline__ void s16_conv_body(const S16Args& a, const int bid_, 
             for (int m = 0; m < MT; ++m) s16_epilogue_tile<EPI>(a, b, (ct * MT + m) * 32 + 4 * half, py + j, px, acc[m * RPW + j]);
         }
     }
-#ifdef TCS_S16_ABLATE
-    __builtin_amdgcn_s_waitcnt(0);                                  // stores acknowledged
-    S16_STAMP(3)
-#endif
 }
 
 template <int KS, int MT, int ROWS, int KSTEPS, int NSTAGE, int STRIDE, int EPI, int RS = 0, int RPW = 1, bool TP = false>
@@ -1073,7 +1036,6 @@ int tcs_conv2d_s16(const tcs_conv_s16_desc* d, tcs_stream_t stream) {
     if (a.in_ws && (d->epilogue != TCS_EPI_DECONV2X || d->Cout % 128 != 0 || (long long)4 * d->H * d->W > (1 << 20))) return TCS_EINVAL;
     a.npx = 0; a.nct = 0; a.npatch = 0;
     a.csplit = (d->tile_cfg / 100000) % 10;            // 0 = cout tile fastest (one weight slice per XCD)
-    a.ablate = d->tile_cfg / 1000000;                  // honoured by -DTCS_S16_ABLATE builds only
     a.bl_cand = nullptr; a.bl_cand_ctot = 0; a.bl_disp = nullptr; a.bl_refined = nullptr; a.bl_delta = nullptr; a.bl_coords1 = nullptr;
     a.bl_flow = nullptr; a.bl_f16 = nullptr; a.bl_f16_groups = 0; a.bl_f16_ch = 0;
     a.warm_pyr0 = a.warm_pyr1 = a.warm_pyr2 = a.warm_pyr3 = nullptr; a.warm_radius = 0;
@@ -1121,7 +1083,7 @@ int tcs_conv2d_s16(const tcs_conv_s16_desc* d, tcs_stream_t stream) {
 }
 
 // Pair kernels exist for the instance combinations the refinement loop groups (core/update.py); any other combination, and
-// anything the planner cannot take (ablation builds), runs as two ordinary launches: the results are the same either way.
+// anything the planner cannot take, runs as two ordinary launches: the results are the same either way.
 }  // extern "C"
 
 template <int NPR>

@@ -3,13 +3,11 @@
 A frame has two parts.  EXTRACT — image normalisation, feature / context networks, correlation pyramid, context convolutions
 (core/tc_stereo.py:101-116,147-149 of the reference) — depends on nothing but the two images.  REFINE — the temporal warp or
 arg-max prior, disparity completion, hidden-state warp and the refinement loop (tc_stereo.py:119-229) — needs EXTRACT's
-features and the previous frame's outputs.  Frames of a sequence are serial through REFINE only, so the EXTRACT of frame t+1
-can be enqueued while the REFINE of frame t still runs: `prefetch(image1, image2)` launches it into the free one
-of two feature slots, and the following `__call__` with the same image tensors finds it there.  What that buys, as measured
-(profiles/r03_frame_phases.txt): the HOST-side launch work of the next EXTRACT (0.35-0.6 ms per frame) leaves
-the frame's serial path; on the GPU the extraction does NOT run beside the loop (its first kernel starts 0.4-1.3 ms after the
-frame's last one — the loop's graph occupies the hardware queues).  Without a prefetch the two stages simply run back to back, as
-the reference does.
+features and the previous frame's outputs.  Both stages are enqueued on the caller's stream and run back to back, as in the
+reference.  A caller that knows its next frame may enqueue that frame's EXTRACT early: `prefetch(image1, image2)` launches it,
+behind the frame in flight, into the free one of two feature slots, and the following `__call__` with the same image tensors
+finds it there.  What that buys, as measured (profiles/r03_frame_phases.txt): the HOST-side launch work of
+the next EXTRACT (0.35-0.6 ms per frame) leaves the frame's serial path.  On the GPU the extraction still runs after the loop.
 
 A `test_mode=False` frame (`outputs=True`: every iteration's predictions, the cost volume) is its own EXTRACT key (the build also writes
 the cost volume) and its own REFINE key (the loop's outputs mode); features prefetched for a test-mode frame are not consumed by it.
@@ -25,16 +23,12 @@ lets the host enqueue frame t+1 while frame t runs.
 from __future__ import annotations
 
 import gc
-import os
 import warnings
 from typing import Callable, Dict, List, Optional
 
 import torch
 
 _CAPTURING = 0          # > 0 while any FrameGraphs capture is recording (FrameGraphs.drop refuses then)
-# EXTRACT is enqueued on the CALLER's stream.  Rounds 3's second stream could not make it overlap the loop on this stack (module docstring) and
-# measured the same (profiles/r04_ab_logs.txt, r4_k); on the caller's stream there are no cross-stream waits to get wrong, and a prefetch
-# only moves the host's launch work ahead.
 
 
 # what the loop's outputs mode adds to the frame's dict (TCStereo._refine_loop(outputs=True))
@@ -62,25 +56,6 @@ def _wants_argmax(temporal):
     return temporal is None or len(temporal) == 8
 
 
-def _tensors(obj, seen=None):
-    """Every torch tensor reachable from a feature bundle (lists, tuples, dicts, objects with __dict__)."""
-    seen = set() if seen is None else seen
-    if id(obj) in seen:
-        return
-    seen.add(id(obj))
-    if torch.is_tensor(obj):
-        yield obj
-    elif isinstance(obj, (list, tuple)):
-        for o in obj:
-            yield from _tensors(o, seen)
-    elif isinstance(obj, dict):
-        for o in obj.values():
-            yield from _tensors(o, seen)
-    elif hasattr(obj, "__dict__"):
-        for o in vars(obj).values():
-            yield from _tensors(o, seen)
-
-
 class _no_gc:
     """No cyclic garbage collection while a stream is capturing.  torch.cuda.graph() collects before it starts capturing; a collection that
     fires DURING the capture and finds an unreachable HIP graph / event of an earlier capture destroys it mid-capture, and the runtime aborts
@@ -102,7 +77,7 @@ class _no_gc:
 
 
 class _Slot:
-    """One of the two feature slots: what the last EXTRACT into it produced, and the events that order its reuse."""
+    """One of the two feature slots: what the last EXTRACT into it produced, and for which images."""
 
     def __init__(self):
         self.feats = None
@@ -111,21 +86,20 @@ class _Slot:
         self.by_prefetch = False
         self.age = 0                           # calls since the features were produced without anybody consuming them
         self.ex_key = None
-        self.ready = torch.cuda.Event()        # EXTRACT done (recorded on the extract stream)
-        self.free = torch.cuda.Event()         # the REFINE that read the features is done (recorded on the caller's stream)
 
 
 class _Entry:
-    def __init__(self, graph, static_in, static_out, graph2=None):
-        self.graph, self.static_in, self.static_out, self.graph2 = graph, static_in, static_out, graph2
+    """A captured stage: its graph (REFINE: the head; `graph2` the loop, and `start` the head's outputs, which the loop graph holds
+    raw pointers to), the static inputs it reads and the outputs it writes."""
+
+    def __init__(self, graph, static_in, static_out, graph2=None, start=None):
+        self.graph, self.static_in, self.static_out, self.graph2, self.start = graph, static_in, static_out, graph2, start
 
 
 class FrameGraphs:
     """`extract_fn(image1, image2, first, outputs) -> feats`, `head_fn(feats, temporal) -> start`, `loop_fn(feats, start, iters, outputs)
     -> dict` (`outputs`: a test_mode=False frame).
-    REFINE is captured as two graphs, the short state-dependent head and the loop, with an event between their launches: a prefetch
-    made right after a frame's call waits for THAT event, so the next frame's EXTRACT runs beside this frame's loop and not beside
-    its head (a chain of small launches that the extractor's 2 400-workgroup launches would starve).
+    REFINE is captured as two graphs, the short state-dependent head and the loop, replayed back to back.
 
     `epoch_fn` returns a value that changes whenever a model parameter is replaced or written in place (`load_state_dict`, an
     optimiser step): a captured graph holds the packed weight images of the moment of capture, so every entry is dropped and
@@ -136,7 +110,6 @@ class FrameGraphs:
                  epoch_fn: Optional[Callable[[], object]] = None, strict: bool = False):
         self.extract_fn, self.head_fn, self.loop_fn = extract_fn, head_fn, loop_fn
         self.warmup, self.epoch_fn, self.strict = warmup, epoch_fn, strict
-        self.loop_start = torch.cuda.Event()   # recorded on the caller's stream between a frame's head and its loop
         self.slots = [_Slot(), _Slot()]
         self.turn = 0                          # the slot the next EXTRACT goes to (unless it still holds unconsumed features)
         self.ex: Dict[tuple, Optional[List[_Entry]]] = {}
@@ -145,7 +118,6 @@ class FrameGraphs:
         self.fell_back = 0
         self.captures = 0
         self.prefetched = 0                    # frames whose EXTRACT had been launched by prefetch()
-        self._sx: Dict[object, torch.cuda.Stream] = {}
 
     # ---- bookkeeping ---------------------------------------------------------------------------------------------------------
     @property
@@ -176,12 +148,6 @@ class FrameGraphs:
         self.slots = [_Slot(), _Slot()]
         self.turn = 0
         gc.collect()
-
-    def _stream(self, device) -> torch.cuda.Stream:
-        st = self._sx.get(device)
-        if st is None:
-            st = self._sx[device] = torch.cuda.Stream(device=device)
-        return st
 
     def _pick_slot(self) -> int:
         """Where the next EXTRACT goes: the slot whose features have been consumed (a prefetch made for the NEXT frame must survive
@@ -216,14 +182,13 @@ class FrameGraphs:
     def _capture_extract(self, key, image1, image2, first, outputs=False) -> Optional[List[_Entry]]:
         static_in = [image1.clone(), image2.clone()]
         run = lambda: self.extract_fn(static_in[0], static_in[1], first, outputs)
-        # The warm-up and the capture write the model's pool buffers, which every extract key of this shape shares: an EXTRACT still in
-        # flight on the extract stream (a prefetch) must be over first, and whatever a slot holds unconsumed is no longer trustworthy.
+        # The warm-up and the capture write the model's pool buffers, which every extract key of this shape shares: whatever a slot
+        # holds unconsumed is no longer trustworthy.
         for sl in self.slots:
             sl.fresh, sl.token = False, None
         try:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
-            side.wait_stream(self._stream(image1.device))
             with torch.cuda.stream(side):
                 for _ in range(self.warmup):        # packs weights, sizes the pools
                     run()
@@ -245,47 +210,38 @@ class FrameGraphs:
             torch.cuda.synchronize()
             return None
 
-    def _launch_extract(self, si: int, image1, image2, first: bool, use_graph: bool, inputs_ready: bool = False, outputs: bool = False):
-        """EXTRACT into slot `si` on the extract stream: after the slot's last reader, and after everything queued on the caller's
-        stream so far (the images are ready) — or, with `inputs_ready` (the images were complete before the latest frame was
-        called), only after that frame's head: the extraction then overlaps its loop."""
+    def _launch_extract(self, si: int, image1, image2, first: bool, use_graph: bool, outputs: bool = False):
+        """EXTRACT into slot `si` on the caller's stream, behind everything already queued there (the slot's last reader included)."""
         slot = self.slots[si]
-        main = torch.cuda.current_stream()
-        sx = main
         key = self._ex_key(image1, first, outputs)
         entries = None
         if use_graph:
             if key not in self.ex:
                 self.ex[key] = self._capture_extract(key, image1, image2, first, outputs)
             entries = self.ex[key]
-        with torch.cuda.stream(sx):
-            if entries is not None:
-                e = entries[si]
-                e.static_in[0].copy_(image1)
-                e.static_in[1].copy_(image2)
-                e.graph.replay()
-                slot.feats = e.static_out
-            else:
-                slot.feats = self.extract_fn(image1, image2, first, outputs)
-                for t in _tensors(slot.feats):       # allocated on the extract stream, read on the caller's: keep the blocks alive for it
-                    t.record_stream(main)
-            slot.ready.record(sx)
+        if entries is not None:
+            e = entries[si]
+            e.static_in[0].copy_(image1)
+            e.static_in[1].copy_(image2)
+            e.graph.replay()
+            slot.feats = e.static_out
+        else:
+            slot.feats = self.extract_fn(image1, image2, first, outputs)
         slot.token, slot.ex_key, slot.fresh, slot.by_prefetch, slot.age = self._token(image1, image2, first, use_graph, outputs), key, True, False, 0
         self.turn = si ^ 1
 
-    def prefetch(self, image1, image2, first: bool = False, use_graph: bool = True, inputs_ready: bool = False) -> int:
+    def prefetch(self, image1, image2, first: bool = False, use_graph: bool = True) -> int:
         """Launch the EXTRACT stage of a coming frame; the next `__call__` with the same image tensor objects (unmodified) uses it.
         `first=True` for a frame that will be called with params=None OR as a mixed batch (params["new_sequence"] present, whatever
         its values): both consume the extract made with the arg-max prior.  A mixed frame does not pick up a `first=False` prefetch.
-        Call it right after the `__call__` it is to overlap with, with `inputs_ready=True` when the images were on the device before
-        that call (see `_launch_extract`).  Returns the slot."""
+        Call it right after the `__call__` it follows.  Returns the slot."""
         self._check_epoch()
         token = self._token(image1, image2, first, use_graph)
         for k in (0, 1):
             if self.slots[k].fresh and self._same(self.slots[k].token, token):
                 return k                                    # already there
         si = self._pick_slot()
-        self._launch_extract(si, image1, image2, first, use_graph, inputs_ready)
+        self._launch_extract(si, image1, image2, first, use_graph)
         self.slots[si].by_prefetch = True
         return si
 
@@ -319,8 +275,7 @@ class FrameGraphs:
                 with _no_gc(), torch.cuda.graph(g2):
                     out = self.loop_fn(feats, start, iters, outputs)
                 g2.replay()
-                entries.append(_Entry(g1, static_in, out, graph2=g2))
-                entries[-1].start = start                 # (the loop graph holds raw pointers to the head graph's outputs)
+                entries.append(_Entry(g1, static_in, out, graph2=g2, start=start))
             torch.cuda.synchronize()
             self.captures += 1
             for sl in self.slots:                       # the capture used both slots: whatever was prefetched into them is gone
@@ -362,14 +317,11 @@ class FrameGraphs:
             self._launch_extract(si, image1, image2, first, use_graph and entries is not None, outputs=outputs)
         slot = self.slots[si]
         slot.fresh, slot.token = False, None            # consumed (and the image tensors are no longer held)
-        main = torch.cuda.current_stream()
-        main.wait_event(slot.ready)
         if entries is not None and self.ex.get(slot.ex_key) is not None and slot.feats is self.ex[slot.ex_key][si].static_out:
             e = entries[si]
             for dst, src in zip(e.static_in, flat):
                 dst.copy_(src)
             e.graph.replay()                            # head
-            self.loop_start.record(main)
             e.graph2.replay()                           # loop
             o = e.static_out
             out = {"flow": o["flow"].clone(), "flow_q": o["flow_q"].clone(), "net_list": [t.clone() for t in o["net_list"]],
@@ -378,12 +330,10 @@ class FrameGraphs:
                 out[k] = o[k].clone()
         else:
             start = self.head_fn(slot.feats, temporal)
-            self.loop_start.record(main)
             if outputs:
                 out = self.loop_fn(slot.feats, start, iters, True)
                 out = dict(out, fmap1=out["fmap1"].clone(), cost_volume=out["cost_volume"].clone())   # (both belong to the slot)
             else:
                 out = self.loop_fn(slot.feats, start, iters)
                 out = dict(out, fmap1=out["fmap1"].clone())      # the slot's tensor is overwritten two frames from now
-        slot.free.record(main)
         return out

@@ -9,6 +9,7 @@ from typing import List, Optional, Sequence
 
 import torch
 
+from . import grouping as _grouping
 from . import native as nv
 
 ACT = {"none": 0, "relu": 1, "sigmoid": 2, "tanh": 3, "leaky": 4, "relu_add_relu": 5}
@@ -554,49 +555,17 @@ def _desc(pc: PackedConv, srcs: Sequence[torch.Tensor]) -> nv.ConvDesc:
     return d
 
 
-_GROUP = None            # (descriptor, name, tensors it points to) of the `with grouped():` block being recorded (LINEAR tcs_conv2d launches)
+_CONV_GROUPS = _grouping.Family("ops", nv.ConvDesc, "tcs_conv2d", "tcs_conv2d_group", "tcs_conv2d_group_fused")
 
 
-class grouped:
+class grouped(_grouping.Grouped):
     """`with ops.grouped(): conv2d(...); conv2d(...)` — two INDEPENDENT tcs_conv2d layers issued as one launch at the end of the block
     where the library has a grouped kernel for them (tcs_conv2d_group), otherwise one after the other; same results either way.
-    The fp32-tensor counterpart of tcs_mi355.s16.grouped.  A recorded descriptor holds raw pointers only, so the block keeps every
-    tensor the call was given (a temporary such as `x.contiguous()` included) alive until the launch."""
-
-    def __init__(self, enabled: bool = True, report: bool = False):
-        self.enabled, self.report = enabled, report
-        self.fused: List[bool] = []          # with `report`: per pair, whether the library issued it as one launch
-
-    def __enter__(self):
-        global _GROUP
-        if self.enabled:
-            if _GROUP is not None:
-                raise RuntimeError("ops.grouped() does not nest")
-            _GROUP = []
-        return self
-
-    def __exit__(self, et, ev, tb):
-        global _GROUP
-        if not self.enabled:
-            return False
-        descs, _GROUP = _GROUP, None
-        if et is not None or not descs:
-            return False
-        for i in range(0, len(descs), 2):
-            chunk = descs[i:i + 2]
-            arr = (C.POINTER(nv.ConvDesc) * len(chunk))(*[C.pointer(d) for d, _, _ in chunk])
-            if self.report:
-                self.fused.append(len(chunk) == 2 and bool(nv.lib().tcs_conv2d_group_fused(arr, 2)))
-            nv.check(nv.lib().tcs_conv2d_group(arr, len(chunk), nv.stream()), "tcs_conv2d_group[" + " | ".join(n for _, n, _ in chunk) + "]")
-        return False
+    The fp32-tensor counterpart of tcs_mi355.s16.grouped (the recorder: tcs_mi355/grouping.py)."""
+    family = _CONV_GROUPS
 
 
-def _launch_conv(d, name: str, keep: tuple):
-    """tcs_conv2d now, or at the end of the enclosing `grouped()` block; `keep`: the objects whose memory `d` points to."""
-    if _GROUP is not None:
-        _GROUP.append((d, name, keep))
-    else:
-        nv.check(nv.lib().tcs_conv2d(C.byref(d), nv.stream()), name)
+_launch_conv = _CONV_GROUPS.launch      # tcs_conv2d now, or at the end of the enclosing `grouped()` block
 
 
 def conv2d(pc: PackedConv, srcs: Sequence[torch.Tensor], act: str = "none", addend=None, post_scale: float = 1.0,

@@ -12,10 +12,11 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, Optional, Sequence
 
 import torch
 
+from . import grouping as _grouping
 from . import native as nv
 from .ops import ACT, EPI_GRU_Q, EPI_GRU_ZR, EPI_LINEAR, MATH_F16X3, PackedConv
 
@@ -28,53 +29,19 @@ def groups_for(C_: int) -> int:
 
 
 # ---- grouped launches (tcs_conv2d_s16_group) -------------------------------------------------------------------------
-_GROUP: Optional[list] = None        # (descriptor, name, tensors it points to) of the `with grouped():` block being recorded
+_CONV_GROUPS = _grouping.Family("s16", nv.ConvS16Desc, "tcs_conv2d_s16", "tcs_conv2d_s16_group", "tcs_conv2d_s16_group_fused")
 
 
-class grouped:
+class grouped(_grouping.Grouped):
     """`with s16.grouped(): a = conv2d(...); b = conv2d(...)` — the (two) tcs_conv2d_s16 launches made inside the block are
     INDEPENDENT layers (neither reads what the other writes) and go out as one launch at the end of the block where the library
     has a pair kernel for their tile instances, otherwise one after the other; the tensors the calls return are valid after the
     block.  What this replaces is a fork / join of two graph branches (tcs_mi355/streams.py): the pair keeps the concurrency
-    without the cross-queue dependencies.  `enabled=False` (A/B runs): launches happen at once, as without the block.  A recorded
-    descriptor holds raw pointers only, so the block keeps every tensor the call was given (temporaries included) alive until the launch."""
-
-    def __init__(self, enabled: bool = True, report: bool = False):
-        self.enabled, self.report = enabled, report
-        self.fused: List[bool] = []          # with `report`: per pair, whether the library issued it as one launch
-
-    def __enter__(self):
-        global _GROUP
-        if self.enabled:
-            if _GROUP is not None:
-                raise RuntimeError("s16.grouped() does not nest")
-            _GROUP = []
-        return self
-
-    def __exit__(self, et, ev, tb):
-        global _GROUP
-        if not self.enabled:
-            return False
-        descs, _GROUP = _GROUP, None
-        if et is not None or not descs:
-            return False
-        for i in range(0, len(descs), 2):
-            chunk = descs[i:i + 2]
-            arr = (C.POINTER(nv.ConvS16Desc) * len(chunk))(*[C.pointer(d) for d, _, _ in chunk])
-            if self.report:
-                self.fused.append(len(chunk) == 2 and bool(nv.lib().tcs_conv2d_s16_group_fused(arr, 2)))
-            nv.check(nv.lib().tcs_conv2d_s16_group(arr, len(chunk), nv.stream()), "tcs_conv2d_s16_group[" + " | ".join(n for _, n, _ in chunk) + "]")
-        return False
+    without the cross-queue dependencies.  The recorder: tcs_mi355/grouping.py."""
+    family = _CONV_GROUPS
 
 
-def _launch(d, name: str, keep: tuple):
-    """tcs_conv2d_s16 now, or at the end of the enclosing `grouped()` block; `keep`: the objects whose memory `d` points to."""
-    if _GROUP is not None:
-        _GROUP.append((d, name, keep))
-    else:
-        nv.check(nv.lib().tcs_conv2d_s16(C.byref(d), nv.stream()), name)
-
-
+_launch = _CONV_GROUPS.launch           # tcs_conv2d_s16 now, or at the end of the enclosing `grouped()` block
 
 
 @dataclass

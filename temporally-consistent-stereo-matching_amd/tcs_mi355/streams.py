@@ -24,7 +24,9 @@ def _hw_queues_allow_forks() -> bool:
     is not available here): the lists of a replayed graph are fed to their queues in batches of consecutive nodes, and a
     batch of the main list can contain a wait for a side-list node that is submitted after it: a pending barrier packet on separate hardware
     queues, a deadlock when the lists share one in-order queue.  ROCclr's default is 4; when
-    the environment asks for fewer, forking is switched off (one launch list: correct on any queue count, ~2 ms per frame slower)."""
+    the environment asks for fewer, forking is switched off (one launch list: correct on any queue count, ~2 ms per frame slower).
+    Only the environment variable is read: on a runtime that hands out fewer queues for another reason, TCS_MI355_STREAMS=0 is the
+    escape hatch."""
     v = os.environ.get("GPU_MAX_HW_QUEUES", "").strip()
     if not v:
         return True
@@ -40,8 +42,6 @@ if ENABLED and not _hw_queues_allow_forks():
     warnings.warn("tcs_mi355: GPU_MAX_HW_QUEUES < 3 — parallel graph branches would deadlock on this few hardware queues; running every frame as "
                   "one launch list (TCS_MI355_STREAMS=0 behaviour)")
     ENABLED = False
-SITES = os.environ.get("TCS_MI355_FORK_SITES", "all").split(",")       # diagnostic: restrict forking to named call sites
-OFF = set(t for t in os.environ.get("TCS_MI355_FORK_OFF", "").split(",") if t)      # diagnostic (A/B runs): call sites that run serially
 # Capture order at a fork.  ROCm's graph executor cuts a captured graph into launch lists by a depth-first walk that follows a node's
 # FIRST captured child: that child stays in its parent's list (same hardware queue, ~1.5 us boundary), every later child starts a
 # new list whose first node waits for the parent across queues (~10 us) and whose last node the join waits for across queues
@@ -56,8 +56,8 @@ _IN_SIDE = 0        # > 0 while a side branch is being enqueued
 
 
 def _side_streams(device, depth: int, n: int, origin: int = 0) -> List[torch.cuda.Stream]:
-    """Side streams of one origin stream and nesting depth: two launch sequences enqueued on different origin streams (the extract
-    stage of the next frame beside the refinement of the current one, tcs_mi355/graph.py) never share a side stream."""
+    """Side streams of one origin stream and nesting depth: two launch sequences enqueued on different origin streams never
+    share a side stream."""
     pool = _POOL.setdefault((device, depth, origin), [])
     while len(pool) < n:
         pool.append(torch.cuda.Stream(device=device))
@@ -101,14 +101,14 @@ def mark():
     return ev
 
 
-def spawn(fn: Callable[[], object], site: str = "", slot: int = 0, after=None) -> Spawned:
+def spawn(fn: Callable[[], object], slot: int = 0, after=None) -> Spawned:
     """Enqueue `fn` on a side stream behind everything already on the current stream and return at once; `join` makes the
     current stream wait for it.  Used for work whose result is needed much later (the next iteration's gru32).  Spawns that
     are in flight at the same time take different `slot`s (one stream each).  `after` (a `mark()`): the side chain starts
     behind THAT point of the current stream instead — work enqueued on the current stream since then neither delays it nor, under
     capture, loses its place as the first child of the fork point (see "Capture order at a fork" above)."""
     global _IN_SIDE, _DEPTH
-    if not ENABLED or _IN_SIDE > 0 or not torch.cuda.is_available() or ("all" not in SITES and site not in SITES) or site in OFF:
+    if not ENABLED or _IN_SIDE > 0 or not torch.cuda.is_available():
         return Spawned(fn(), None)
     cur = torch.cuda.current_stream()
     pool = _POOL.setdefault((cur.device, "spawn", cur.cuda_stream), [])
@@ -137,11 +137,11 @@ def join(h: Spawned):
     return None if h is None else h.result
 
 
-def fork_join(fns: Sequence[Callable[[], object]], site: str = "") -> list:
+def fork_join(fns: Sequence[Callable[[], object]]) -> list:
     """Run fns[0] on the current stream and fns[1:] on side streams; returns their results after joining.
     Every side chain starts after everything already enqueued on the current stream and the current stream waits for
     every side chain before continuing, so memory handed between the chains is ordered."""
-    if not ENABLED or len(fns) <= 1 or not torch.cuda.is_available() or ("all" not in SITES and site not in SITES) or site in OFF:
+    if not ENABLED or len(fns) <= 1 or not torch.cuda.is_available():
         return [f() for f in fns]
     global _DEPTH, _IN_SIDE
     if _IN_SIDE > 0:

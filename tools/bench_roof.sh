@@ -1,12 +1,11 @@
 #!/bin/bash
-# bench.py with the roofline pass but without CPU baseline / extra legs, per TCS_MI355_X variant; prints frame time and the lookup's in-frame clock.
-# usage: tools/bench_roof.sh <out dir under gpurun_out> <variant> [<variant> ...]     ("-" = default)
+# bench.py with the roofline pass but without CPU baseline / extra legs, per library variant; prints frame time and the lookup's in-frame clock.
+# usage: tools/bench_roof.sh <output subdirectory> <variant> [<variant> ...]     ("-" = the default library, "name" = lib/libtcs_mi355_name.so)
 out=gpurun_out/$1; shift; mkdir -p $out
 for v in "$@"; do
-  x=${v%%@*}; [ "$x" = "-" ] && x=""
-  lib=""; [[ "$v" == *@* ]] && lib=$(pwd)/temporally-consistent-stereo-matching_amd/lib/libtcs_mi355_${v#*@}.so      # "tokens@libvariant"
+  lib=""; [ "$v" != "-" ] && lib=$(pwd)/temporally-consistent-stereo-matching_amd/lib/libtcs_mi355_$v.so      # tools/build_variant.sh
   [ -n "$lib" ] && export TCS_MI355_LIB=$lib || unset TCS_MI355_LIB
-  TCS_MI355_X=$x timeout -k 10 300 python bench.py --full --steps 20 --no-cpu-baseline --batched-leg 0 --drop-in-steps 0 --kitti-steps 0 2>/dev/null > $out/bench_$v.json || { echo "[$v] FAILED"; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 20 --no-cpu-baseline --batched-leg 0 --drop-in-steps 0 --kitti-steps 0 2>/dev/null > $out/bench_$v.json || { echo "[$v] FAILED"; exit 1; }
   python - "$out/bench_$v.json" "$v" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]

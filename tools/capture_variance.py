@@ -3,7 +3,7 @@
 dropped between attempts) and replays each capture for 8 frames: mean, per-frame GPU time (events) and per-frame HOST time
 of the enqueue (no sync).  Finding (profiles/r02_step_jitter.txt): every capture replays at the same speed; slow means come
 from bursts of individual slow frames (50-60 ms), i.e. from the box, not from the graph.  (GPU box.)
-usage: capture_variance.py [captures] ; env TCS_MI355_X / TCS_MI355_FORK_SITES select the schedule."""
+usage: capture_variance.py [captures] ; env TCS_MI355_STREAMS=0 selects the one-list schedule."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -2,7 +2,7 @@
 """Run-to-run determinism of one non-temporal frame (no splat atomics on that path): the same inputs through the eager
 schedule N times and through the HIP-graph replay N times; prints the max abs difference of the up-sampled disparity
 against the first eager run.  A schedule without races gives exact zeros in every column (GPU box).
-usage: determinism_check.py [iters] [runs] ; env TCS_MI355_X / TCS_MI355_STREAMS select the schedule."""
+usage: determinism_check.py [iters] [runs] ; env TCS_MI355_STREAMS=0 selects the one-list schedule."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -43,5 +43,5 @@ for r in range(1, len(sums)):
             print(f"eager run {r}: first divergence in iteration {it}: {bad}")
             break
 ref = outs[0][1]
-print(f"X=[{os.environ.get('TCS_MI355_X', '')}] STREAMS={os.environ.get('TCS_MI355_STREAMS', '1')} iters={iters}: " +
+print(f"STREAMS={os.environ.get('TCS_MI355_STREAMS', '1')} iters={iters}: " +
       " ".join(f"{k}:{float((o - ref).abs().max()):.1e}" for k, o in outs))

@@ -32,7 +32,7 @@ def scan(path: str):
         if not m or kname is None:
             continue
         ops = [o.strip() for o in m.group(2).split(",")]
-        addr = (ops[0] if m.group(1).startswith(("ds_write", "ds_store")) else (ops[1] if len(ops) > 1 else "")).split()[0] if ops else ""
+        addr = (ops[0] if m.group(1).startswith("ds_write") else (ops[1] if len(ops) > 1 else "")).split()[0] if ops else ""
         if not re.match(r"v\d+$", addr):
             continue
         for j in range(i - 1, max(i - 400, 0), -1):
