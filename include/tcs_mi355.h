@@ -39,7 +39,8 @@ int tcs_abi_version(void);                 /* bumped when a signature changes (7
                                               last field of tcs_conv_desc and tcs_conv_s16_desc; 9: the ordered splat entry points;
                                               10: tcs_conv2d_group_fused; 11: the *_mixed entry points;
                                               12: tcs_convex_upsample_pair, tcs_resize_bilinear_scaled; 13: the tcs_*loss* entry points;
-                                              14: tcs_corr_lookup_backward, tcs_corr_build_backward*) */
+                                              14: tcs_corr_lookup_backward, tcs_corr_build_backward*;
+                                              15: tcs_loss_finish_counts, the tcs_*loss*_bwd entry points) */
 const char* tcs_error_string(int code);
 
 /* ------------------------------------------------------------------------------------------------
@@ -624,6 +625,38 @@ int tcs_grad_normal_loss(const float* grad_preds, long long grad_stride, const f
 /* the partials of `parts` -> out [TCS_LOSS_NOUT] (fp64) and out32 [5]; loss_weights: a HOST array of `iters` doubles */
 int tcs_loss_finish(const double* workspace, int parts, int B, int H, int W, int iters, int k, const double* loss_weights, double* out,
                     float* out32, tcs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The objective's backward.  Gradients of the four losses with respect to every prediction, float32,
+ * each output element written exactly once (zeros included; no memset, no atomics: two calls are bit-equal).  Nothing is read on
+ * the host: `upstream` is the DEVICE vector of five float32 d/d out32 (TCS_LOSS_OUT_TOTAL .. TCS_LOSS_OUT_GRAD: a part's effective
+ * coefficient is its own entry plus the total's entry times the part's weight in the total, 1, 1, 0.25, 5), `counts` the DEVICE vector
+ * tcs_loss_finish_counts wrote; a count of 0 (an empty mask) gives all-zero gradients.  loss_weights: a HOST array of `iters` doubles.
+ * Masks, targets and arguments are the forward's; gradient buffers have the layout of the predictions they belong to.
+ * ---------------------------------------------------------------------------------------------- */
+#define TCS_LOSS_COUNT_SEQ 0    /* valid full-resolution pixels */
+#define TCS_LOSS_COUNT_INIT 1   /* init_loss's quarter-resolution mask */
+#define TCS_LOSS_COUNT_NORM 2
+#define TCS_LOSS_COUNT_GRAD 3
+#define TCS_LOSS_NCOUNTS 4
+/* tcs_loss_finish, and the mask counts of `parts` (0 for an absent part) into counts [TCS_LOSS_NCOUNTS] (fp64, device) */
+int tcs_loss_finish_counts(const double* workspace, int parts, int B, int H, int W, int iters, int k, const double* loss_weights,
+                           double* out, float* out32, double* counts, tcs_stream_t stream);
+/* sequence_loss: any of grad_preds (layout of preds), grad_mono, grad_init may be NULL (not wanted), not all three */
+int tcs_sequence_loss_bwd(const float* preds, long long iter_stride, long long refine_offset, int iters, const float* flow_gt,
+                          const void* valid, int valid_mode, const float* flow_mono, const float* flow_init, int B, int H, int W,
+                          const double* loss_weights, const double* counts, const float* upstream, float* grad_preds, float* grad_mono,
+                          float* grad_init, tcs_stream_t stream);
+/* init_loss: the whole of grad_cost_volume [B,D,H/4,W/4] is written.  Among equal real values at the top-k boundary the lowest
+ * candidate index is taken first; a zero-filled candidate takes a slot and receives nothing; a hinge of exactly 0 passes gradient */
+int tcs_init_loss_bwd(const float* cost_volume, int D, const float* flow_gt, const void* valid, int valid_mode, int B, int H, int W, int k,
+                      float threshold, const double* counts, const float* upstream, float* grad_cost_volume, tcs_stream_t stream);
+/* disp_grad_loss and disp_normal_loss: grad_preds / q_preds as in tcs_grad_normal_loss, either may be NULL with its outputs */
+int tcs_grad_normal_loss_bwd(const float* grad_preds, long long grad_stride, const float* q_preds, long long q_stride,
+                             long long q_refine_offset, int iters, const float* grad_gt, const uint8_t* grad_mask, const uint8_t* grad_valid,
+                             const float* norm_gt, const uint8_t* norm_mask, const uint8_t* norm_valid, int B, int H, int W,
+                             const double* loss_weights, const double* counts, const float* upstream, float* grad_grad_preds,
+                             float* grad_q_preds, tcs_stream_t stream);
 
 #ifdef __cplusplus
 }

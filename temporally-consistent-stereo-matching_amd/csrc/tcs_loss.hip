@@ -288,6 +288,42 @@ __global__ __launch_bounds__(LOSS_NT) void k_sequence_loss(SeqArgs a) {
 // coalesced along w1), the masked top-K in registers.  Slots: sum of phi_gt over the mask, mask count, the clipped top-K sum, the
 // forward-mask count over all pixels, non-finite count.
 // ---------------------------------------------------------------------------------------------------------------------------------
+// The per-pixel geometry of init_loss (train_stereo.py:141-160) at quarter pixel p of [B,h,w]: the mask, the clipped index and its two
+// gathered entries, phi_gt, and the +-1.5 exclusion window.  One definition for the forward and the backward: the backward's mask
+// and hinge are the forward's, bit for bit.
+struct InitPixel {
+    bool mask;
+    int x, df, i0, i1;           // the gathered entries col[i0] (weight 1 - t) and col[i1] (weight t)
+    float fs, t, phi, lo, hi;
+    const float* col;            // cost_volume[b, :, y, x], stride cs
+    long long cs;
+};
+
+__device__ __forceinline__ InitPixel init_pixel(const float* __restrict__ cv, int D, const float* __restrict__ flow,
+                                                const void* __restrict__ valid, int vmode, int H, int W, int h, int w, long long p) {
+    InitPixel g;
+    const int x = (int)(p % w), y = (int)((p / w) % h), b = (int)(p / ((long long)h * w));
+    const long long img = (long long)b * H * W;
+    const float fs = 0.25f * flow[img + (long long)(4 * y) * W + 4 * x];          // nearest, x scale
+    const bool ok = bilinear_is_one(valid, vmode, flow, img, H, W, h, w, y, x) && sqrt_rn(fs * fs) < 175.f;
+    const float dmax = (float)(D - 1);
+    const float idx = (float)x - (-fs);
+    g.mask = ok && idx >= 0.f && idx <= dmax;
+    const float ic = fminf(fmaxf(idx, 0.f), dmax);
+    g.col = cv + (long long)b * D * h * w + (long long)y * w + x;
+    g.cs = (long long)h * w;
+    g.x = x;
+    g.fs = fs;
+    g.df = (int)floorf(ic);
+    g.t = ic - (float)g.df;
+    g.i1 = min(max(g.df + 1, 0), D - 1);
+    g.i0 = min(max(g.df, 0), D - 1);
+    g.phi = g.t * g.col[g.i1 * g.cs] + (1.f - g.t) * g.col[g.i0 * g.cs];
+    g.lo = ic - 1.5f;
+    g.hi = ic + 1.5f;
+    return g;
+}
+
 template <int K>
 __global__ __launch_bounds__(LOSS_NT) void k_init_loss(const float* __restrict__ cv, int D, const float* __restrict__ flow,
                                                        const void* __restrict__ valid, int vmode, int B, int H, int W, float threshold,
@@ -298,20 +334,11 @@ __global__ __launch_bounds__(LOSS_NT) void k_init_loss(const float* __restrict__
     const long long p = (long long)blockIdx.x * LOSS_NT + threadIdx.x;
     double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     if (p < n) {
-        const int x = (int)(p % w), y = (int)((p / w) % h), b = (int)(p / ((long long)h * w));
-        const long long img = (long long)b * H * W;
-        const float fs = 0.25f * flow[img + (long long)(4 * y) * W + 4 * x];          // nearest, x scale
-        const bool ok = bilinear_is_one(valid, vmode, flow, img, H, W, h, w, y, x) && sqrt_rn(fs * fs) < 175.f;
-        const float dmax = (float)(D - 1);
-        const float idx = (float)x - (-fs);
-        const bool mask = ok && idx >= 0.f && idx <= dmax;
-        const float ic = fminf(fmaxf(idx, 0.f), dmax);
-        const float* col = cv + (long long)b * D * h * w + (long long)y * w + x;
-        const long long cs = (long long)h * w;
-        const int df = (int)floorf(ic);
-        const float t = ic - (float)df;
-        const float phi = t * col[min(max(df + 1, 0), D - 1) * cs] + (1.f - t) * col[min(max(df, 0), D - 1) * cs];
-        const float lo = ic - 1.5f, hi = ic + 1.5f;
+        const InitPixel g = init_pixel(cv, D, flow, valid, vmode, H, W, h, w, p);
+        const bool mask = g.mask;
+        const float* col = g.col;
+        const long long cs = g.cs;
+        const float phi = g.phi, lo = g.lo, hi = g.hi;
         float top[K];
 #pragma unroll
         for (int j = 0; j < K; ++j) top[j] = -INFINITY;
@@ -450,6 +477,7 @@ struct FinishArgs {
     double weights[TCS_LOSS_MAX_ITERS];
     double* out;
     float* out32;
+    double* counts;              // [TCS_LOSS_NCOUNTS] mask counts for the backward kernels, or NULL
 };
 
 __global__ __launch_bounds__(FIN_NT) void k_loss_finish(FinishArgs a) {
@@ -511,6 +539,240 @@ __global__ __launch_bounds__(FIN_NT) void k_loss_finish(FinishArgs a) {
     o[TCS_LOSS_OUT_FLAGS] = flags;
     for (int i = 0; i < TCS_LOSS_NOUT; ++i) a.out[i] = o[i];
     for (int i = 0; i < 5; ++i) a.out32[i] = (float)o[i];
+    if (a.counts) {                                     // a part that is absent counts 0: its backward then writes zeros
+        a.counts[TCS_LOSS_COUNT_SEQ] = (a.parts & TCS_LOSS_SEQ) ? sq[a.iters + 2] : 0.0;
+        a.counts[TCS_LOSS_COUNT_INIT] = (a.parts & TCS_LOSS_INIT) ? in[1] : 0.0;
+        a.counts[TCS_LOSS_COUNT_NORM] = (a.parts & TCS_LOSS_NORM) ? gn[3 * a.iters + 1] : 0.0;
+        a.counts[TCS_LOSS_COUNT_GRAD] = (a.parts & TCS_LOSS_GRAD) ? gn[3 * a.iters] : 0.0;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The backward kernels.  Every loss is a masked mean, so a gradient is a sign or a short stencil times
+// upstream * weight / count.  The upstream gradient (the five float32 of d/d out32: total, seq, init, norm, grad) and the counts (the
+// finish's TCS_LOSS_COUNT_* vector) are read from device memory: no host synchronisation.  Coefficients are formed in fp64 and
+// rounded once; a count of 0 (an empty mask) gives coefficient 0, never NaN.  Every output element is written exactly once by one
+// thread, zeros included: no memset, no atomics, two backwards are bit-equal.
+// ---------------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double inv_count(const double* counts, int which) {
+    const double n = counts[which];
+    return n > 0.0 ? 1.0 / n : 0.0;
+}
+
+// torch.sign / the backward of abs: 0 at 0 (and at NaN)
+__device__ __forceinline__ float sign_of(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
+
+struct SeqBwdArgs {
+    const float* preds;          // as SeqArgs
+    float* g_preds;              // same layout as preds, or NULL
+    long long it_stride, ref_off;
+    int iters;
+    const float* gt;
+    const void* valid;
+    int vmode;
+    const float* mono;
+    const float* init;
+    float* g_mono;               // or NULL
+    float* g_init;               // or NULL
+    long long n;
+    const double* counts;
+    const float* upstream;
+    double weights[TCS_LOSS_MAX_ITERS];
+};
+
+// the forward's layout: SEQ_PIX pixels per thread, gt and mask read once into registers, iters x 2 + 2 maps read and written once
+__global__ __launch_bounds__(LOSS_NT) void k_sequence_loss_bwd(SeqBwdArgs a) {
+    const long long base = (long long)blockIdx.x * LOSS_NT * SEQ_PIX + threadIdx.x;
+    const double c = ((double)a.upstream[TCS_LOSS_OUT_TOTAL] + (double)a.upstream[TCS_LOSS_OUT_SEQ]) * inv_count(a.counts, TCS_LOSS_COUNT_SEQ);
+    float g[SEQ_PIX];
+    bool m[SEQ_PIX], in[SEQ_PIX];
+#pragma unroll
+    for (int j = 0; j < SEQ_PIX; ++j) {
+        const long long p = base + (long long)j * LOSS_NT;
+        in[j] = p < a.n;
+        g[j] = in[j] ? a.gt[p] : 0.f;
+        m[j] = in[j] && valid_at(a.valid, a.vmode, a.gt, p) != 0.f;
+    }
+    if (a.g_preds)
+        for (int it = 0; it < a.iters; ++it) {
+            const float* q = a.preds + it * a.it_stride;
+            float* gq = a.g_preds + it * a.it_stride;
+            const float cq = (float)(c * a.weights[it]), cr = (float)(c * a.weights[it] * 1.2);
+#pragma unroll
+            for (int j = 0; j < SEQ_PIX; ++j) {
+                if (!in[j]) continue;
+                const long long p = base + (long long)j * LOSS_NT;
+                const float qv = q[p], rv = q[a.ref_off + p];
+                gq[p] = m[j] ? sign_of(qv - g[j]) * cq : 0.f;
+                gq[a.ref_off + p] = m[j] ? sign_of(rv - g[j]) * cr : 0.f;
+            }
+        }
+    const float c01 = (float)(c * 0.1);
+#pragma unroll
+    for (int j = 0; j < SEQ_PIX; ++j) {
+        if (!in[j]) continue;
+        const long long p = base + (long long)j * LOSS_NT;
+        if (a.g_mono) a.g_mono[p] = m[j] ? sign_of(a.mono[p] - g[j]) * c01 : 0.f;
+        if (a.g_init) a.g_init[p] = m[j] ? sign_of(a.init[p] - g[j]) * c01 : 0.f;
+    }
+}
+
+struct GradNormBwdArgs {
+    const float* grad_preds;     // as GradNormArgs; NULL = no gradient-loss backward
+    float* g_grad;               // same layout as grad_preds
+    long long grad_stride;
+    const float* q_preds;        // NULL = no normal-loss backward
+    float* g_q;                  // same layout as q_preds
+    long long q_stride, q_ref_off;
+    int iters;
+    const float* grad_gt;
+    const uint8_t* grad_mask;
+    const uint8_t* grad_valid;
+    const float* norm_gt;
+    const uint8_t* norm_mask;
+    const uint8_t* norm_valid;
+    int B, h, w;
+    const double* counts;
+    const float* upstream;
+    double weights[TCS_LOSS_MAX_ITERS];
+};
+
+// d(loss pixel)/d(gx, gy) of 0.5 * mean_c |n - n_gt| + 0.5 * (1 - n . n_gt), n = (gx, gy, -1) / sqrt(gx^2 + gy^2 + 1), at the loss pixel
+// whose own / right / lower values of flow_q are f00, f01, f10 (gx = f00 - f01, gy = f00 - f10: the differences of -flow).  The signs
+// come from the forward's fp32 normal (normal_loss_at's operations), the magnitudes are fp64.
+__device__ __forceinline__ void normal_loss_dg(float f00, float f01, float f10, const float (&ng)[3], double& dgx, double& dgy) {
+    const float d00 = -f00, d01 = -f01, d10 = -f10;
+    const float gx = d01 - d00, gy = d10 - d00;
+    const float nr = normal_rnorm_denominator(gx, gy);
+    const float n0 = div_rn(gx, nr), n1 = div_rn(gy, nr), n2 = div_rn(-1.f, nr);
+    const double a0 = (double)sign_of(n0 - ng[0]) / 6.0 - 0.5 * (double)ng[0];
+    const double a1 = (double)sign_of(n1 - ng[1]) / 6.0 - 0.5 * (double)ng[1];
+    const double a2 = (double)sign_of(n2 - ng[2]) / 6.0 - 0.5 * (double)ng[2];
+    const double x = (double)gx, y = (double)gy;
+    const double ir = 1.0 / sqrt((x * x + y * y) + 1.0);
+    const double m0 = x * ir, m1 = y * ir, m2 = -ir;
+    const double an = (a0 * m0 + a1 * m1) + a2 * m2;
+    dgx = (a0 - an * m0) * ir;
+    dgy = (a1 - an * m1) * ir;
+}
+
+// One thread per quarter pixel and iteration (blockIdx.y).  The normal loss is a gather: pixel (y, x) collects from the loss pixels (y, x), (y, x-1) and (y-1, x);
+// at the last column / row the replicate pad makes the difference identically 0, so that term is absent.  The mask is the loss pixel's.
+__global__ __launch_bounds__(LOSS_NT) void k_grad_normal_loss_bwd(GradNormBwdArgs a) {
+    const long long hw = (long long)a.h * a.w, n = (long long)a.B * hw;
+    const long long p = (long long)blockIdx.x * LOSS_NT + threadIdx.x;
+    if (p >= n) return;
+    const int x = (int)(p % a.w), y = (int)((p / a.w) % a.h), b = (int)(p / hw);
+    const long long q = (long long)y * a.w + x;
+    const int it = blockIdx.y;
+    const double up0 = (double)a.upstream[TCS_LOSS_OUT_TOTAL];
+    if (a.grad_preds) {
+        const bool mg = a.grad_valid[p] && a.grad_mask[p];
+        const float g0t = a.grad_gt[(long long)b * 2 * hw + q], g1t = a.grad_gt[((long long)b * 2 + 1) * hw + q];
+        const double c = (5.0 * up0 + (double)a.upstream[TCS_LOSS_OUT_GRAD]) * inv_count(a.counts, TCS_LOSS_COUNT_GRAD) * 0.5;
+        const long long o = it * a.grad_stride + (long long)b * 2 * hw + q;
+        const float ci = (float)(c * a.weights[it]);
+        a.g_grad[o] = mg ? sign_of(a.grad_preds[o] - g0t) * ci : 0.f;
+        a.g_grad[o + hw] = mg ? sign_of(a.grad_preds[o + hw] - g1t) * ci : 0.f;
+    }
+    if (a.q_preds) {
+        // loss pixels: 0 = (y, x), 1 = (y, x-1), 2 = (y-1, x)
+        const bool has1 = x >= 1, has2 = y >= 1;
+        const long long pl[3] = {p, has1 ? p - 1 : p, has2 ? p - a.w : p};
+        bool mn[3];
+        float ng[3][3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            mn[k] = a.norm_valid[pl[k]] && a.norm_mask[pl[k]];
+            const long long ql = pl[k] - (long long)b * hw;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) ng[k][c] = a.norm_gt[((long long)b * 3 + c) * hw + ql];
+        }
+        mn[1] = mn[1] && has1;
+        mn[2] = mn[2] && has2;
+        const bool xin = x < a.w - 1, yin = y < a.h - 1;     // the loss pixel (y, x)'s own differences exist
+        const int xr = min(x + 1, a.w - 1), yd = min(y + 1, a.h - 1), xl = max(x - 1, 0), yu = max(y - 1, 0);
+        const double c = (0.25 * up0 + (double)a.upstream[TCS_LOSS_OUT_NORM]) * inv_count(a.counts, TCS_LOSS_COUNT_NORM);
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const long long o = it * a.q_stride + r * a.q_ref_off + (long long)b * hw;
+            const float* f = a.q_preds + o;
+            const float fc = f[q];
+            double s = 0.0, dgx, dgy;
+            if (mn[0]) {
+                normal_loss_dg(fc, f[(long long)y * a.w + xr], f[(long long)yd * a.w + x], ng[0], dgx, dgy);
+                s += (xin ? dgx : 0.0) + (yin ? dgy : 0.0);
+            }
+            if (mn[1]) {                                 // (y, x-1): this pixel is its right neighbour
+                normal_loss_dg(f[(long long)y * a.w + xl], fc, f[(long long)yd * a.w + xl], ng[1], dgx, dgy);
+                s -= dgx;
+            }
+            if (mn[2]) {                                 // (y-1, x): this pixel is its lower neighbour
+                normal_loss_dg(f[(long long)yu * a.w + x], f[(long long)yu * a.w + xr], fc, ng[2], dgx, dgy);
+                s -= dgy;
+            }
+            a.g_q[o + q] = (float)(s * (c * a.weights[it] * (r ? 1.2 : 1.0)));
+        }
+    }
+}
+
+// One thread per quarter pixel walks its column as k_init_loss does, keeps the top-K with their indices (a strict > insertion: among
+// equal values the lowest index comes first; a zero-filled candidate carries index -1 and receives nothing), and writes the whole
+// column: -(1 - t) / N and -t / N on the two gathered entries, +1 / (K N) on every real top-K entry whose hinge is >= 0, 0 elsewhere.
+template <int K>
+__global__ __launch_bounds__(LOSS_NT) void k_init_loss_bwd(const float* __restrict__ cv, float* __restrict__ g_cv, int D,
+                                                           const float* __restrict__ flow, const void* __restrict__ valid, int vmode,
+                                                           int B, int H, int W, float threshold, const double* __restrict__ counts,
+                                                           const float* __restrict__ upstream) {
+    const int h = H / 4, w = W / 4;
+    const long long n = (long long)B * h * w;
+    const long long p = (long long)blockIdx.x * LOSS_NT + threadIdx.x;
+    if (p >= n) return;
+    const InitPixel g = init_pixel(cv, D, flow, valid, vmode, H, W, h, w, p);
+    float* out = g_cv + (g.col - cv);
+    if (!g.mask) {
+        for (int c = 0; c < D; ++c) out[c * g.cs] = 0.f;
+        return;
+    }
+    float top[K];
+    int ti[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        top[j] = -INFINITY;
+        ti[j] = -1;
+    }
+    for (int c = 0; c < D; ++c) {
+        const float fc = (float)c;
+        const bool excl = fc >= g.lo && fc < g.hi;
+        float val = excl ? 0.f : g.col[c * g.cs];
+        int vi = excl ? -1 : c;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            const float cur = top[j];
+            const int ci = ti[j];
+            const bool gt = val > cur;
+            top[j] = gt ? val : cur;
+            ti[j] = gt ? vi : ci;
+            val = gt ? cur : val;
+            vi = gt ? ci : vi;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+        if (!(((top[j] + threshold) - g.phi) >= 0.f)) ti[j] = -1;
+    const double c0 = ((double)upstream[TCS_LOSS_OUT_TOTAL] + (double)upstream[TCS_LOSS_OUT_INIT]) * inv_count(counts, TCS_LOSS_COUNT_INIT);
+    // the clipped index in fp64 around the forward's floor: x + fs is exact there
+    const double t = fmin(fmax((double)g.x + (double)g.fs, 0.0), (double)(D - 1)) - (double)g.df;
+    const double cnm = c0 / (double)K;
+    for (int c = 0; c < D; ++c) {
+        double v = 0.0;
+        if (c == g.i0) v -= (1.0 - t) * c0;
+        if (c == g.i1) v -= t * c0;
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+            if (ti[j] == c) v += cnm;
+        out[c * g.cs] = (float)v;
+    }
 }
 
 struct LossLayout {
@@ -533,6 +795,32 @@ LossLayout loss_layout(int B, int H, int W, int iters) {
 
 bool shape_ok(int B, int H, int W) {
     return B > 0 && H >= 4 && W >= 4 && (long long)B * H * W <= 0x7fffffffLL;
+}
+
+int loss_finish_launch(const double* workspace, int parts, int B, int H, int W, int iters, int k, const double* loss_weights,
+                       double* out, float* out32, double* counts, tcs_stream_t stream) {
+    if (!workspace || !out || !out32 || parts <= 0 || parts > 15) return TCS_EINVAL;
+    if (!shape_ok(B, H, W) || iters < 1 || iters > TCS_LOSS_MAX_ITERS || k < 1 || k > LOSS_MAX_K) return TCS_EINVAL;
+    if ((parts & (TCS_LOSS_SEQ | TCS_LOSS_GRAD | TCS_LOSS_NORM)) && !loss_weights) return TCS_EINVAL;
+    const LossLayout L = loss_layout(B, H, W, iters);
+    FinishArgs a{};
+    a.part = workspace;
+    a.parts = parts;
+    a.iters = iters;
+    a.k = k;
+    a.seq_blocks = L.seq_blocks;
+    a.init_blocks = L.init_blocks;
+    a.gn_blocks = L.gn_blocks;
+    a.seq_off = L.seq_off;
+    a.init_off = L.init_off;
+    a.gn_off = L.gn_off;
+    a.quarter_pixels = (double)B * (H / 4) * (W / 4);
+    for (int i = 0; i < iters; ++i) a.weights[i] = loss_weights ? loss_weights[i] : 0.0;
+    a.out = out;
+    a.out32 = out32;
+    a.counts = counts;
+    hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(FIN_NT), 0, tcs_stream(stream), a);
+    return tcs_launch_status();
 }
 
 }  // namespace
@@ -612,26 +900,91 @@ int tcs_grad_normal_loss(const float* grad_preds, long long grad_stride, const f
 
 int tcs_loss_finish(const double* workspace, int parts, int B, int H, int W, int iters, int k, const double* loss_weights, double* out,
                     float* out32, tcs_stream_t stream) {
-    if (!workspace || !out || !out32 || parts <= 0 || parts > 15) return TCS_EINVAL;
-    if (!shape_ok(B, H, W) || iters < 1 || iters > TCS_LOSS_MAX_ITERS || k < 1 || k > LOSS_MAX_K) return TCS_EINVAL;
-    if ((parts & (TCS_LOSS_SEQ | TCS_LOSS_GRAD | TCS_LOSS_NORM)) && !loss_weights) return TCS_EINVAL;
-    const LossLayout L = loss_layout(B, H, W, iters);
-    FinishArgs a{};
-    a.part = workspace;
-    a.parts = parts;
+    return loss_finish_launch(workspace, parts, B, H, W, iters, k, loss_weights, out, out32, nullptr, stream);
+}
+
+int tcs_loss_finish_counts(const double* workspace, int parts, int B, int H, int W, int iters, int k, const double* loss_weights,
+                           double* out, float* out32, double* counts, tcs_stream_t stream) {
+    if (!counts) return TCS_EINVAL;
+    return loss_finish_launch(workspace, parts, B, H, W, iters, k, loss_weights, out, out32, counts, stream);
+}
+
+int tcs_sequence_loss_bwd(const float* preds, long long iter_stride, long long refine_offset, int iters, const float* flow_gt,
+                          const void* valid, int valid_mode, const float* flow_mono, const float* flow_init, int B, int H, int W,
+                          const double* loss_weights, const double* counts, const float* upstream, float* grad_preds, float* grad_mono,
+                          float* grad_init, tcs_stream_t stream) {
+    if (!preds || !flow_gt || !valid || !flow_mono || !flow_init || !loss_weights || !counts || !upstream) return TCS_EINVAL;
+    if (!grad_preds && !grad_mono && !grad_init) return TCS_EINVAL;
+    if (!shape_ok(B, H, W) || iters < 1 || iters > TCS_LOSS_MAX_ITERS || valid_mode < 0 || valid_mode > 2) return TCS_EINVAL;
+    SeqBwdArgs a{};
+    a.preds = preds;
+    a.g_preds = grad_preds;
+    a.it_stride = iter_stride;
+    a.ref_off = refine_offset;
     a.iters = iters;
-    a.k = k;
-    a.seq_blocks = L.seq_blocks;
-    a.init_blocks = L.init_blocks;
-    a.gn_blocks = L.gn_blocks;
-    a.seq_off = L.seq_off;
-    a.init_off = L.init_off;
-    a.gn_off = L.gn_off;
-    a.quarter_pixels = (double)B * (H / 4) * (W / 4);
-    for (int i = 0; i < iters; ++i) a.weights[i] = loss_weights ? loss_weights[i] : 0.0;
-    a.out = out;
-    a.out32 = out32;
-    hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(FIN_NT), 0, tcs_stream(stream), a);
+    a.gt = flow_gt;
+    a.valid = valid;
+    a.vmode = valid_mode;
+    a.mono = flow_mono;
+    a.init = flow_init;
+    a.g_mono = grad_mono;
+    a.g_init = grad_init;
+    a.n = (long long)B * H * W;
+    a.counts = counts;
+    a.upstream = upstream;
+    for (int i = 0; i < iters; ++i) a.weights[i] = loss_weights[i];
+    hipLaunchKernelGGL(k_sequence_loss_bwd, dim3(loss_layout(B, H, W, iters).seq_blocks), dim3(LOSS_NT), 0, tcs_stream(stream), a);
+    return tcs_launch_status();
+}
+
+int tcs_init_loss_bwd(const float* cost_volume, int D, const float* flow_gt, const void* valid, int valid_mode, int B, int H, int W, int k,
+                      float threshold, const double* counts, const float* upstream, float* grad_cost_volume, tcs_stream_t stream) {
+    if (!cost_volume || !flow_gt || !valid || !counts || !upstream || !grad_cost_volume) return TCS_EINVAL;
+    if (!shape_ok(B, H, W) || D < 1 || k < 1 || k > LOSS_MAX_K || k > D || valid_mode < 0 || valid_mode > 2) return TCS_EINVAL;
+    if ((long long)B * D * (H / 4) * (W / 4) > 0x7fffffffLL) return TCS_EUNSUPPORTED;
+    const dim3 g(tcs_cdiv((long long)B * (H / 4) * (W / 4), LOSS_NT)), t(LOSS_NT);
+    hipStream_t s = tcs_stream(stream);
+#define TCS_INIT_K(KK) \
+    case KK: hipLaunchKernelGGL(k_init_loss_bwd<KK>, g, t, 0, s, cost_volume, grad_cost_volume, D, flow_gt, valid, valid_mode, B, H, W, \
+                                threshold, counts, upstream); break;
+    switch (k) {
+        TCS_INIT_K(1) TCS_INIT_K(2) TCS_INIT_K(3) TCS_INIT_K(4) TCS_INIT_K(5) TCS_INIT_K(6) TCS_INIT_K(7) TCS_INIT_K(8)
+    }
+#undef TCS_INIT_K
+    return tcs_launch_status();
+}
+
+int tcs_grad_normal_loss_bwd(const float* grad_preds, long long grad_stride, const float* q_preds, long long q_stride,
+                             long long q_refine_offset, int iters, const float* grad_gt, const uint8_t* grad_mask, const uint8_t* grad_valid,
+                             const float* norm_gt, const uint8_t* norm_mask, const uint8_t* norm_valid, int B, int H, int W,
+                             const double* loss_weights, const double* counts, const float* upstream, float* grad_grad_preds,
+                             float* grad_q_preds, tcs_stream_t stream) {
+    if ((!grad_preds && !q_preds) || !loss_weights || !counts || !upstream) return TCS_EINVAL;
+    if (grad_preds && (!grad_gt || !grad_mask || !grad_valid || !grad_grad_preds)) return TCS_EINVAL;
+    if (q_preds && (!norm_gt || !norm_mask || !norm_valid || !grad_q_preds)) return TCS_EINVAL;
+    if (!shape_ok(B, H, W) || iters < 1 || iters > TCS_LOSS_MAX_ITERS) return TCS_EINVAL;
+    GradNormBwdArgs a{};
+    a.grad_preds = grad_preds;
+    a.g_grad = grad_grad_preds;
+    a.grad_stride = grad_stride;
+    a.q_preds = q_preds;
+    a.g_q = grad_q_preds;
+    a.q_stride = q_stride;
+    a.q_ref_off = q_refine_offset;
+    a.iters = iters;
+    a.grad_gt = grad_gt;
+    a.grad_mask = grad_mask;
+    a.grad_valid = grad_valid;
+    a.norm_gt = norm_gt;
+    a.norm_mask = norm_mask;
+    a.norm_valid = norm_valid;
+    a.B = B;
+    a.h = H / 4;
+    a.w = W / 4;
+    a.counts = counts;
+    a.upstream = upstream;
+    for (int i = 0; i < iters; ++i) a.weights[i] = loss_weights[i];
+    hipLaunchKernelGGL(k_grad_normal_loss_bwd, dim3(loss_layout(B, H, W, iters).gn_blocks, iters), dim3(LOSS_NT), 0, tcs_stream(stream), a);
     return tcs_launch_status();
 }
 

@@ -535,7 +535,7 @@ int tcs_avgpool3s2(const float* x, int B, int C, int H, int W, float* out, tcs_s
     return tcs_launch_status();
 }
 
-int tcs_abi_version(void) { return 14; }
+int tcs_abi_version(void) { return 15; }
 
 const char* tcs_error_string(int code) {
     switch (code) {

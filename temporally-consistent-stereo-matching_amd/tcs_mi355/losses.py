@@ -5,10 +5,12 @@ in five launches and one host synchronisation.
 Every function returns what the reference's returns: a 0-d float32 device tensor and a dict of Python floats under the same keys.
 The arithmetic is in tcs_loss.hip (per element fp32 in the reference's order, sums in fp64 finished in a fixed order, so two calls
 are bit-equal).  The reference's NaN / Inf asserts become a device-side count that is read with the metrics and raised here as
-FloatingPointError.  There is no autograd: inputs that require grad raise NotImplementedError (DESIGN.md sections 1, 12, 13).
+FloatingPointError.  This module computes values only: inputs that require grad raise NotImplementedError (DESIGN.md sections 1,
+12, 13); tcs_mi355.train_losses is the same objective with autograd, built on the plans and launches below (section 15).
 Only the reference's scale 1/4 (n_downsample 2) and max_flow 700 are supported; anything else raises ValueError."""
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import Dict, List, Sequence, Tuple
 
 import torch
@@ -56,8 +58,8 @@ def _no_grad(**tensors):
             if isinstance(x, (list, tuple)):
                 _no_grad(**{name: x})
             elif torch.is_tensor(x) and x.requires_grad:
-                raise NotImplementedError(f"{name} requires grad: the MI355X objective computes values only, it builds no autograd "
-                                          f"graph (detach the inputs, or use the reference's PyTorch losses for training)")
+                raise NotImplementedError(f"{name} requires grad: tcs_mi355.losses computes values only, it builds no autograd graph "
+                                          f"(detach the inputs, or use tcs_mi355.train_losses, the differentiable objective)")
 
 
 def _shape(t, name, ndim, c=None):
@@ -108,11 +110,16 @@ def _weights(w, n):
     return w[:n]
 
 
+def _carries_grad(base, views) -> bool:
+    """The base may stand for its views unless a view was made a leaf of its own (then only torch.stack carries its gradient)."""
+    return base.requires_grad or not any(v.requires_grad for v in views)
+
+
 def _stacked(entries: Sequence[torch.Tensor], shape) -> torch.Tensor:
     """The one tensor [len(entries), *shape] whose slices the entries are (forward(test_mode=False)'s lists), or a stacked copy."""
     n = len(entries)
     base = entries[0]._base
-    if (base is not None and base.is_contiguous() and base.dtype == torch.float32 and tuple(base.shape) == (n, *shape)
+    if (base is not None and _carries_grad(base, entries) and base.is_contiguous() and base.dtype == torch.float32 and tuple(base.shape) == (n, *shape)
             and all(e._base is base and e.data_ptr() == base[i].data_ptr() and e.is_contiguous() for i, e in enumerate(entries))):
         return base
     return torch.stack([e.float() for e in entries]).contiguous()
@@ -128,7 +135,7 @@ def _stacked_pairs(pairs, shape) -> torch.Tensor:
             raise ValueError(f"prediction shape {tuple(t.shape)} != {tuple(shape)}")
     n = len(pairs)
     base = flat[0]._base
-    if (base is not None and base.is_contiguous() and base.dtype == torch.float32 and tuple(base.shape) == (n, 2, *shape)
+    if (base is not None and _carries_grad(base, flat) and base.is_contiguous() and base.dtype == torch.float32 and tuple(base.shape) == (n, 2, *shape)
             and all(t._base is base and t.data_ptr() == base[i // 2, i % 2].data_ptr() for i, t in enumerate(flat))):
         return base
     return torch.stack([torch.stack([p[0].float(), p[1].float()]) for p in pairs]).contiguous()
@@ -145,12 +152,50 @@ def _read(out: torch.Tensor) -> List[float]:
 
 
 # ---------------------------------------------------------------------------------------------
-# the reference's four losses
+# plans: a validated call, as the tensors and numbers its launches need.  The public functions below and tcs_mi355.train_losses
+# both build a plan and hand it to _launch, so the two modules validate and launch the same way.
 # ---------------------------------------------------------------------------------------------
-def sequence_loss(flow_mono, flow_init, flow_preds, flow_gt, valid, loss_weights):
-    """train_stereo.py:94-135: 0.1 L1(flow_init) + 0.1 L1(flow_mono) + sum_i w_i mean(|q_i - gt| + 1.2 |r_i - gt|) over the mask,
-    and the EPE metrics of the last iteration."""
-    _no_grad(flow_mono=flow_mono, flow_init=flow_init, flow_preds=flow_preds, flow_gt=flow_gt, valid=valid)
+def _plan(parts, B, H, W, n, gt, v, mode, **kw):
+    p = SimpleNamespace(parts=parts, B=B, H=H, W=W, n=n, k=1, thres=0.0, weights=None, gt=gt, v=v, vmode=mode, init_iters=1,
+                        up=None, mono=None, init=None, cv=None, q=None, grad=None, targets=None, dense_gt=True,
+                        grad_gt=None, grad_mask=None, grad_valid=None, norm_gt=None, norm_mask=None, norm_valid=None)
+    for key, val in kw.items():
+        setattr(p, key, val)
+    return p
+
+
+def _launch(p, counts: bool = False):
+    """The launches of a plan: the quarter-resolution targets (if a quarter loss is in it), the partial sums, the finish.
+    -> (out, out32) or, with counts=True, (out, out32, counts); the targets stay on the plan for the backward."""
+    if p.targets == "flow":
+        p.grad_gt, p.norm_gt, p.grad_mask, p.norm_mask, vdense, vsparse = ops.loss_targets(p.gt, p.v, p.vmode)
+        p.grad_valid = p.norm_valid = vdense if p.dense_gt else vsparse
+    elif p.targets == "full":
+        pooled, gmask, vdense, vsparse = ops.loss_targets_full(p.gt, p.v, p.vmode)
+        t = (pooled, gmask, vdense if p.dense_gt else vsparse)
+        if p.parts == ops.LOSS_GRAD:
+            p.grad_gt, p.grad_mask, p.grad_valid = t
+        else:
+            p.norm_gt, p.norm_mask, p.norm_valid = t
+    ws = ops.loss_workspace(p.B, p.H, p.W, p.n, p.gt.device)
+    if p.parts & ops.LOSS_SEQ:
+        ops.sequence_loss_partials(p.up, p.gt, p.v, p.vmode, p.mono, p.init, ws)
+    if p.parts & ops.LOSS_INIT:
+        ops.init_loss_partials(p.cv, p.gt, p.v, p.vmode, p.k, p.thres, p.init_iters, ws)
+    if p.parts & (ops.LOSS_GRAD | ops.LOSS_NORM):
+        ops.grad_normal_loss_partials(p.grad, p.q, _grad_targets(p), _norm_targets(p), ws, p.H, p.W)
+    return ops.loss_finish(ws, p.parts, p.B, p.H, p.W, p.n, p.k, p.weights, counts=counts)
+
+
+def _grad_targets(p):
+    return (p.grad_gt, p.grad_mask, p.grad_valid) if p.grad is not None else None
+
+
+def _norm_targets(p):
+    return (p.norm_gt, p.norm_mask, p.norm_valid) if p.q is not None else None
+
+
+def _plan_sequence(flow_mono, flow_init, flow_preds, flow_gt, valid, loss_weights):
     _shape(flow_gt, "flow_gt", 4, c=1)
     B, _, H, W = (int(s) for s in flow_gt.shape)
     n = len(flow_preds)
@@ -165,17 +210,10 @@ def sequence_loss(flow_mono, flow_init, flow_preds, flow_gt, valid, loss_weights
     gt, mono, init = _f32(flow_gt, "flow_gt"), _f32(flow_mono, "flow_mono"), _f32(flow_init, "flow_init")
     _device(gt.device, valid=v, flow_mono=mono, flow_init=init, flow_preds=flow_preds[0][0])
     preds = _stacked_pairs(flow_preds, (B, 1, H, W))
-    ws = ops.loss_workspace(B, H, W, n, gt.device)
-    ops.sequence_loss_partials(preds, gt, v, mode, mono, init, ws)
-    out, out32 = ops.loss_finish(ws, ops.LOSS_SEQ, B, H, W, n, 1, w)
-    r = _read(out)
-    return out32[1], {k: r[_IDX[k]] for k in SEQ_KEYS}
+    return _plan(ops.LOSS_SEQ, B, H, W, n, gt, v, mode, weights=w, up=preds, mono=mono, init=init)
 
 
-def init_loss(cost_volume, flow_gt, valid, max_flow=700, k=1, scale=0.25, threshold=0.1):
-    """train_stereo.py:138-180 on cost_volume [B,D,H/4,W/4]: 1 - mean phi(gt) plus the hinge of the top-k zero-filled candidates
-    outside [gt-1.5, gt+1.5), k <= min(8, D)."""
-    _no_grad(cost_volume=cost_volume, flow_gt=flow_gt, valid=valid)
+def _plan_init(cost_volume, flow_gt, valid, max_flow, k, scale, threshold):
     _shape(flow_gt, "flow_gt", 4, c=1)
     _shape(cost_volume, "cost_volume", 4)
     _scale(scale)
@@ -191,34 +229,20 @@ def init_loss(cost_volume, flow_gt, valid, max_flow=700, k=1, scale=0.25, thresh
     v, mode = _valid(valid, B, H, W)
     gt, cv = _f32(flow_gt, "flow_gt"), _f32(cost_volume, "cost_volume")
     _device(gt.device, valid=v, cost_volume=cv)
-    ws = ops.loss_workspace(B, H, W, 1, gt.device)
-    ops.init_loss_partials(cv, gt, v, mode, k, threshold, 1, ws)
-    out, out32 = ops.loss_finish(ws, ops.LOSS_INIT, B, H, W, 1, k, None)
-    r = _read(out)
-    return out32[2], {k_: r[_IDX[k_]] for k_ in INIT_KEYS}
+    return _plan(ops.LOSS_INIT, B, H, W, 1, gt, v, mode, k=k, thres=float(threshold), cv=cv)
 
 
-def _quarter_loss(preds_stacked, gt_full, valid, loss_weights, dense_gt, part, n):
+def _plan_quarter(preds_stacked, gt_full, valid, loss_weights, dense_gt, part, n):
     B, Cc, H, W = (int(s) for s in gt_full.shape)
     v, mode = _valid(valid, B, H, W)
     gt = _f32(gt_full, "gt")
     _device(gt.device, valid=v, predictions=preds_stacked)
     w = _weights(loss_weights, n)
-    pooled, gmask, vdense, vsparse = ops.loss_targets_full(gt, v, mode)
-    t = (pooled, gmask, vdense if dense_gt else vsparse)
-    ws = ops.loss_workspace(B, H, W, n, gt.device)
-    if part == ops.LOSS_GRAD:
-        ops.grad_normal_loss_partials(preds_stacked, None, t, None, ws, H, W)
-    else:
-        ops.grad_normal_loss_partials(None, preds_stacked, None, t, ws, H, W)
-    out, out32 = ops.loss_finish(ws, part, B, H, W, n, 1, w)
-    return out, out32
+    which = {"grad": preds_stacked} if part == ops.LOSS_GRAD else {"q": preds_stacked}
+    return _plan(part, B, H, W, n, gt, v, mode, weights=w, targets="full", dense_gt=bool(dense_gt), **which)
 
 
-def disp_grad_loss(disp_grad_preds, disp_grad_gt, valid, loss_weights, metric_name='grad_loss', scale=0.25, dense_gt=True):
-    """train_stereo.py:41-64: the full-resolution GT gradient [B,2,H,W] median-pooled 4x4, masked |GT| < 5 and by the dense
-    (max-pooled) or sparse (bilinear == 1) valid mask; sum_i w_i mean_c |pred_i - GT|."""
-    _no_grad(disp_grad_preds=disp_grad_preds, disp_grad_gt=disp_grad_gt, valid=valid)
+def _plan_disp_grad(disp_grad_preds, disp_grad_gt, valid, loss_weights, scale, dense_gt):
     _shape(disp_grad_gt, "disp_grad_gt", 4, c=2)
     _scale(scale)
     B, _, H, W = (int(s) for s in disp_grad_gt.shape)
@@ -228,45 +252,30 @@ def disp_grad_loss(disp_grad_preds, disp_grad_gt, valid, loss_weights, metric_na
         if tuple(p.shape) != (B, 2, H // 4, W // 4):
             raise ValueError(f"disp_grad prediction shape {tuple(p.shape)} != {(B, 2, H // 4, W // 4)}")
     preds = _stacked(disp_grad_preds, (B, 2, H // 4, W // 4))
-    out, out32 = _quarter_loss(preds, disp_grad_gt, valid, loss_weights, dense_gt, ops.LOSS_GRAD, n)
-    r = _read(out)
-    return out32[4], {metric_name: r[_IDX["grad_loss"]]}
+    return _plan_quarter(preds, disp_grad_gt, valid, loss_weights, dense_gt, ops.LOSS_GRAD, n)
 
 
-def disp_normal_loss(flow_q_preds, disp_norm_gt, valid, loss_weights, metric_name='norm_loss', scale=0.25, dense_gt=True):
-    """train_stereo.py:67-91: the full-resolution GT normal [B,3,H,W] median-pooled 4x4, masked n_x/n_z, n_y/n_z < 5; the normals
-    of -flow_q and -flow_q_refine of every iteration, 0.5 mean|dn| + 0.5 (1 - n.n_gt), the refined one weighted 1.2."""
-    _no_grad(flow_q_preds=flow_q_preds, disp_norm_gt=disp_norm_gt, valid=valid)
+def _plan_disp_normal(flow_q_preds, disp_norm_gt, valid, loss_weights, scale, dense_gt):
     _shape(disp_norm_gt, "disp_norm_gt", 4, c=3)
     _scale(scale)
     B, _, H, W = (int(s) for s in disp_norm_gt.shape)
     n = len(flow_q_preds)
     _check_iters(n)
     preds = _stacked_pairs(flow_q_preds, (B, 1, H // 4, W // 4))
-    out, out32 = _quarter_loss(preds, disp_norm_gt, valid, loss_weights, dense_gt, ops.LOSS_NORM, n)
-    r = _read(out)
-    return out32[3], {metric_name: r[_IDX["norm_loss"]]}
+    return _plan_quarter(preds, disp_norm_gt, valid, loss_weights, dense_gt, ops.LOSS_NORM, n)
 
 
-# ---------------------------------------------------------------------------------------------
-# the whole objective
-# ---------------------------------------------------------------------------------------------
-def training_objective(training_output: Dict, flow: torch.Tensor, valid: torch.Tensor, init_k: int = 3, init_thres: float = 0.5,
-                       n_downsample: int = 2, dense_gt: bool = True, sync: bool = True):
-    """train_stereo.py:362-399 for one frame: `flow` [B,1,H,W] and the dataset's `valid` [B,H,W] (or [B,1,H,W]) as the trainer
-    reads them; `dense_gt=False` is the trainer's kitti_raw setting.  Five launches: the quarter-resolution targets (straight
-    from the flow, no full-resolution gradient), the sequence loss, the init loss, the gradient and normal losses, the finish.
+_OUTPUT_KEYS = ("flow_predictions", "flow_q_predictions", "disp_grad_q_predictions", "flow_mono", "flow_init", "cost_volume")
 
-    sync=True: returns (total, metrics): total = seq + init + 0.25 norm + 5 grad as a 0-d float32 device tensor, metrics the
-    reference's merged dict (SEQ_KEYS, INIT_KEYS, 'norm_loss', 'grad_loss'), read with the one host synchronisation.
-    sync=False: returns (total, vector) with no synchronisation: vector is a float64 device tensor in OBJECTIVE_KEYS order
-    ('nonfinite' last: bit 0 flow predictions, bit 1 cost volume, bit 2 gradient predictions; not raised in this mode)."""
-    keys = ("flow_predictions", "flow_q_predictions", "disp_grad_q_predictions", "flow_mono", "flow_init", "cost_volume")
-    missing = [k for k in keys if k not in training_output]
+
+def _output_tensors(training_output):
+    missing = [k for k in _OUTPUT_KEYS if k not in training_output]
     if missing:
         raise ValueError(f"training_output lacks {missing}: call forward(..., test_mode=False)")
-    to = training_output
-    _no_grad(flow=flow, valid=valid, **{k: to[k] for k in keys})
+    return {k: training_output[k] for k in _OUTPUT_KEYS}
+
+
+def _plan_objective(to, flow, valid, init_k, init_thres, n_downsample, dense_gt):
     if int(n_downsample) != 2:
         raise ValueError(f"n_downsample {n_downsample}: the MI355X objective supports the reference's 2 only")
     _shape(flow, "flow", 4, c=1)
@@ -301,17 +310,84 @@ def training_objective(training_output: Dict, flow: torch.Tensor, valid: torch.T
     grad = _stacked(to["disp_grad_q_predictions"], (B, 2, h, w))
     _device(gt.device, valid=v, flow_mono=mono, flow_init=init, cost_volume=cv, flow_predictions=up, flow_q_predictions=q,
             disp_grad_q_predictions=grad)
-    T = ops.VALID_TRAINER
-    grad_gt, norm_gt, gmask, nmask, vdense, vsparse = ops.loss_targets(gt, v, T)
-    vq = vdense if dense_gt else vsparse
-    ws = ops.loss_workspace(B, H, W, n, gt.device)
-    ops.sequence_loss_partials(up, gt, v, T, mono, init, ws)
-    ops.init_loss_partials(cv, gt, v, T, k, init_thres, n, ws)
-    ops.grad_normal_loss_partials(grad, q, (grad_gt, gmask, vq), (norm_gt, nmask, vq), ws, H, W)
     parts = ops.LOSS_SEQ | ops.LOSS_INIT | ops.LOSS_GRAD | ops.LOSS_NORM
-    out, out32 = ops.loss_finish(ws, parts, B, H, W, n, k, wts)
+    return _plan(parts, B, H, W, n, gt, v, ops.VALID_TRAINER, k=k, thres=float(init_thres), weights=wts, init_iters=n, up=up,
+                 mono=mono, init=init, cv=cv, q=q, grad=grad, targets="flow", dense_gt=bool(dense_gt))
+
+
+# what each function returns from the finished vectors (out: float64 in OBJECTIVE_KEYS order, out32: the five losses as float32)
+def _sequence_result(out, out32):
+    r = _read(out)
+    return out32[1], {k: r[_IDX[k]] for k in SEQ_KEYS}
+
+
+def _init_result(out, out32):
+    r = _read(out)
+    return out32[2], {k_: r[_IDX[k_]] for k_ in INIT_KEYS}
+
+
+def _disp_grad_result(out, out32, metric_name):
+    r = _read(out)
+    return out32[4], {metric_name: r[_IDX["grad_loss"]]}
+
+
+def _disp_normal_result(out, out32, metric_name):
+    r = _read(out)
+    return out32[3], {metric_name: r[_IDX["norm_loss"]]}
+
+
+def _objective_result(out, out32, sync):
     if not sync:
         return out32[0], out
     r = _read(out)
     metrics = {key: r[_IDX[key]] for key in SEQ_KEYS + INIT_KEYS + ("norm_loss", "grad_loss")}
     return out32[0], metrics
+
+
+# ---------------------------------------------------------------------------------------------
+# the reference's four losses
+# ---------------------------------------------------------------------------------------------
+def sequence_loss(flow_mono, flow_init, flow_preds, flow_gt, valid, loss_weights):
+    """train_stereo.py:94-135: 0.1 L1(flow_init) + 0.1 L1(flow_mono) + sum_i w_i mean(|q_i - gt| + 1.2 |r_i - gt|) over the mask,
+    and the EPE metrics of the last iteration."""
+    _no_grad(flow_mono=flow_mono, flow_init=flow_init, flow_preds=flow_preds, flow_gt=flow_gt, valid=valid)
+    return _sequence_result(*_launch(_plan_sequence(flow_mono, flow_init, flow_preds, flow_gt, valid, loss_weights)))
+
+
+def init_loss(cost_volume, flow_gt, valid, max_flow=700, k=1, scale=0.25, threshold=0.1):
+    """train_stereo.py:138-180 on cost_volume [B,D,H/4,W/4]: 1 - mean phi(gt) plus the hinge of the top-k zero-filled candidates
+    outside [gt-1.5, gt+1.5), k <= min(8, D)."""
+    _no_grad(cost_volume=cost_volume, flow_gt=flow_gt, valid=valid)
+    return _init_result(*_launch(_plan_init(cost_volume, flow_gt, valid, max_flow, k, scale, threshold)))
+
+
+def disp_grad_loss(disp_grad_preds, disp_grad_gt, valid, loss_weights, metric_name='grad_loss', scale=0.25, dense_gt=True):
+    """train_stereo.py:41-64: the full-resolution GT gradient [B,2,H,W] median-pooled 4x4, masked |GT| < 5 and by the dense
+    (max-pooled) or sparse (bilinear == 1) valid mask; sum_i w_i mean_c |pred_i - GT|."""
+    _no_grad(disp_grad_preds=disp_grad_preds, disp_grad_gt=disp_grad_gt, valid=valid)
+    return _disp_grad_result(*_launch(_plan_disp_grad(disp_grad_preds, disp_grad_gt, valid, loss_weights, scale, dense_gt)), metric_name)
+
+
+def disp_normal_loss(flow_q_preds, disp_norm_gt, valid, loss_weights, metric_name='norm_loss', scale=0.25, dense_gt=True):
+    """train_stereo.py:67-91: the full-resolution GT normal [B,3,H,W] median-pooled 4x4, masked n_x/n_z, n_y/n_z < 5; the normals
+    of -flow_q and -flow_q_refine of every iteration, 0.5 mean|dn| + 0.5 (1 - n.n_gt), the refined one weighted 1.2."""
+    _no_grad(flow_q_preds=flow_q_preds, disp_norm_gt=disp_norm_gt, valid=valid)
+    return _disp_normal_result(*_launch(_plan_disp_normal(flow_q_preds, disp_norm_gt, valid, loss_weights, scale, dense_gt)), metric_name)
+
+
+# ---------------------------------------------------------------------------------------------
+# the whole objective
+# ---------------------------------------------------------------------------------------------
+def training_objective(training_output: Dict, flow: torch.Tensor, valid: torch.Tensor, init_k: int = 3, init_thres: float = 0.5,
+                       n_downsample: int = 2, dense_gt: bool = True, sync: bool = True):
+    """train_stereo.py:362-399 for one frame: `flow` [B,1,H,W] and the dataset's `valid` [B,H,W] (or [B,1,H,W]) as the trainer
+    reads them; `dense_gt=False` is the trainer's kitti_raw setting.  Five launches: the quarter-resolution targets (straight
+    from the flow, no full-resolution gradient), the sequence loss, the init loss, the gradient and normal losses, the finish.
+
+    sync=True: returns (total, metrics): total = seq + init + 0.25 norm + 5 grad as a 0-d float32 device tensor, metrics the
+    reference's merged dict (SEQ_KEYS, INIT_KEYS, 'norm_loss', 'grad_loss'), read with the one host synchronisation.
+    sync=False: returns (total, vector) with no synchronisation: vector is a float64 device tensor in OBJECTIVE_KEYS order
+    ('nonfinite' last: bit 0 flow predictions, bit 1 cost volume, bit 2 gradient predictions; not raised in this mode)."""
+    to = _output_tensors(training_output)
+    _no_grad(flow=flow, valid=valid, **to)
+    return _objective_result(*_launch(_plan_objective(to, flow, valid, init_k, init_thres, n_downsample, dense_gt)), sync)

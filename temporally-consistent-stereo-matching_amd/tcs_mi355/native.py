@@ -154,6 +154,12 @@ SIGNATURES = {
     "tcs_grad_normal_loss": (c_int, [c_fp, C.c_longlong, c_fp, C.c_longlong, C.c_longlong, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
                                      c_int, c_int, c_int, c_fp, c_fp]),
     "tcs_loss_finish": (c_int, [c_fp, c_int, c_int, c_int, c_int, c_int, c_int, C.POINTER(C.c_double), c_fp, c_fp, c_fp]),
+    "tcs_loss_finish_counts": (c_int, [c_fp, c_int, c_int, c_int, c_int, c_int, c_int, C.POINTER(C.c_double), c_fp, c_fp, c_fp, c_fp]),
+    "tcs_sequence_loss_bwd": (c_int, [c_fp, C.c_longlong, C.c_longlong, c_int, c_fp, c_fp, c_int, c_fp, c_fp, c_int, c_int, c_int,
+                                      C.POINTER(C.c_double), c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "tcs_init_loss_bwd": (c_int, [c_fp, c_int, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_f, c_fp, c_fp, c_fp, c_fp]),
+    "tcs_grad_normal_loss_bwd": (c_int, [c_fp, C.c_longlong, c_fp, C.c_longlong, C.c_longlong, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
+                                         c_int, c_int, c_int, C.POINTER(C.c_double), c_fp, c_fp, c_fp, c_fp, c_fp]),
 }
 
 

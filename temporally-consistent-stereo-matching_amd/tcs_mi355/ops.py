@@ -661,6 +661,7 @@ LOSS_KEYS = ("loss", "seq_loss", "init_loss", "norm_loss", "grad_loss", "epe", "
 LOSS_SEQ, LOSS_INIT, LOSS_GRAD, LOSS_NORM = 1, 2, 4, 8
 LOSS_MAX_ITERS, LOSS_MAX_K = 64, 8
 VALID_VALUES, VALID_TRAINER, VALID_BOOL = 0, 1, 2      # valid_mode of the tcs_*loss* entry points
+LOSS_NCOUNTS = 4                                       # TCS_LOSS_COUNT_*: seq, init, norm, grad
 
 
 def _u8(t: torch.Tensor) -> torch.Tensor:
@@ -740,11 +741,77 @@ def grad_normal_loss_partials(grad_preds, q_preds, grad_t, norm_t, ws: torch.Ten
                                            nv.ptr(ws, "workspace", torch.float64), nv.stream()), "tcs_grad_normal_loss")
 
 
-def loss_finish(ws: torch.Tensor, parts: int, B: int, H: int, W: int, iters: int, k: int, weights):
-    """The partials of `parts` -> (out [len(LOSS_KEYS)] float64, out32 [5] float32: loss, seq, init, norm, grad) on the device."""
+def loss_finish(ws: torch.Tensor, parts: int, B: int, H: int, W: int, iters: int, k: int, weights, counts: bool = False):
+    """The partials of `parts` -> (out [len(LOSS_KEYS)] float64, out32 [5] float32: loss, seq, init, norm, grad) on the device;
+    counts=True: the same launch also writes the mask counts the backward kernels divide by, (out, out32, counts [4] float64)."""
     w = (C.c_double * max(iters, 1))(*[float(x) for x in weights]) if weights is not None else None
     out = torch.empty(len(LOSS_KEYS), dtype=torch.float64, device=ws.device)
     out32 = torch.empty(5, dtype=torch.float32, device=ws.device)
+    if counts:
+        cnt = torch.empty(LOSS_NCOUNTS, dtype=torch.float64, device=ws.device)
+        nv.check(nv.lib().tcs_loss_finish_counts(nv.ptr(ws, "workspace", torch.float64), int(parts), B, H, W, int(iters), int(k), w,
+                                                 nv.ptr(out, dtype=torch.float64), nv.ptr(out32), nv.ptr(cnt, dtype=torch.float64),
+                                                 nv.stream()), "tcs_loss_finish_counts")
+        return out, out32, cnt
     nv.check(nv.lib().tcs_loss_finish(nv.ptr(ws, "workspace", torch.float64), int(parts), B, H, W, int(iters), int(k), w,
                                       nv.ptr(out, dtype=torch.float64), nv.ptr(out32), nv.stream()), "tcs_loss_finish")
     return out, out32
+
+
+# the backward of the objective (DESIGN.md section 15).  `counts` is loss_finish(counts=True)'s vector and `upstream` the float32 [5]
+# gradient of out32, both on the device: nothing here reads them on the host.  Every returned buffer is written whole by its kernel.
+def _host_weights(weights, iters: int):
+    return (C.c_double * iters)(*[float(x) for x in weights[:iters]])
+
+
+def _f64(t):
+    return nv.ptr(t, "counts", torch.float64)
+
+
+def sequence_loss_backward(preds, flow_gt, valid, valid_mode: int, flow_mono, flow_init, weights, counts, upstream,
+                           want_preds: bool = True, want_mono: bool = True, want_init: bool = True):
+    """-> (grad of the stacked [iters, 2, B, 1, H, W] predictions, grad flow_mono, grad flow_init); None where not wanted."""
+    iters, _, B, _, H, W = (int(s) for s in preds.shape)
+    n = B * H * W
+    g_preds = torch.empty_like(preds) if want_preds else None
+    g_mono = torch.empty_like(flow_mono) if want_mono else None
+    g_init = torch.empty_like(flow_init) if want_init else None
+    nv.check(nv.lib().tcs_sequence_loss_bwd(nv.ptr(preds, "preds"), 2 * n, n, iters, nv.ptr(flow_gt, "flow_gt"),
+                                            _valid_ptr(valid, valid_mode), valid_mode, nv.ptr(flow_mono, "flow_mono"),
+                                            nv.ptr(flow_init, "flow_init"), B, H, W, _host_weights(weights, iters), _f64(counts),
+                                            nv.ptr(upstream, "upstream"), nv.ptr(g_preds), nv.ptr(g_mono), nv.ptr(g_init), nv.stream()),
+             "tcs_sequence_loss_bwd")
+    return g_preds, g_mono, g_init
+
+
+def init_loss_backward(cost_volume, flow_gt, valid, valid_mode: int, k: int, threshold: float, counts, upstream):
+    """-> the gradient of cost_volume [B,D,h,w]."""
+    B, D = int(cost_volume.shape[0]), int(cost_volume.shape[1])
+    H, W = int(flow_gt.shape[2]), int(flow_gt.shape[3])
+    g = torch.empty_like(cost_volume)
+    nv.check(nv.lib().tcs_init_loss_bwd(nv.ptr(cost_volume, "cost_volume"), D, nv.ptr(flow_gt, "flow_gt"), _valid_ptr(valid, valid_mode),
+                                        valid_mode, B, H, W, int(k), float(threshold), _f64(counts), nv.ptr(upstream, "upstream"),
+                                        nv.ptr(g), nv.stream()), "tcs_init_loss_bwd")
+    return g
+
+
+def grad_normal_loss_backward(grad_preds, q_preds, grad_t, norm_t, H: int, W: int, weights, counts, upstream):
+    """grad_preds / q_preds / grad_t / norm_t as grad_normal_loss_partials (None = that loss is not differentiated)
+    -> (grad of grad_preds, grad of q_preds)."""
+    ref = grad_preds if grad_preds is not None else q_preds
+    iters = int(ref.shape[0])
+    B, h, w = int(ref.shape[-4] if grad_preds is None else ref.shape[1]), int(ref.shape[-2]), int(ref.shape[-1])
+    nq = B * h * w
+    g = grad_t if grad_t is not None else (None, None, None)
+    m = norm_t if norm_t is not None else (None, None, None)
+    u8 = torch.uint8
+    g_grad = torch.empty_like(grad_preds) if grad_preds is not None else None
+    g_q = torch.empty_like(q_preds) if q_preds is not None else None
+    nv.check(nv.lib().tcs_grad_normal_loss_bwd(nv.ptr(grad_preds, "disp_grad_preds"), 2 * nq, nv.ptr(q_preds, "flow_q_preds"), 2 * nq, nq,
+                                               iters, nv.ptr(g[0], "grad_gt"), nv.ptr(_u8(g[1]) if g[1] is not None else None, dtype=u8),
+                                               nv.ptr(_u8(g[2]) if g[2] is not None else None, dtype=u8), nv.ptr(m[0], "norm_gt"),
+                                               nv.ptr(_u8(m[1]) if m[1] is not None else None, dtype=u8),
+                                               nv.ptr(_u8(m[2]) if m[2] is not None else None, dtype=u8), B, H, W,
+                                               _host_weights(weights, iters), _f64(counts), nv.ptr(upstream, "upstream"),
+                                               nv.ptr(g_grad), nv.ptr(g_q), nv.stream()), "tcs_grad_normal_loss_bwd")
+    return g_grad, g_q

@@ -72,7 +72,7 @@ def torch_objective(out, flow, valid, k=3, thr=0.5):
     cand = torch.arange(D, device=cv.device).view(1, -1, 1, 1)
     excl = ((cand >= idx - 1.5) & (cand < idx + 1.5)) | ~mask
     top = torch.topk(cv.masked_fill(excl, 0), k=k, dim=1).values
-    nml = (top + thr - phi).clamp(min=0)[mask.repeat(1, k, 1, 1)].mean()
+    nml = (top + thr - phi.detach()).clamp(min=0)[mask.repeat(1, k, 1, 1)].mean()     # train_stereo.py:171 (same value; matters under backward)
     ini = gl + nml
     m.update(init_loss=ini.item(), init_gt_loss=gl.item(), init_nm_loss=nml.item(),
              forward_mask_rate=((top[:, :1] + 0.3 - phi) > 0).float().mean().item())
