@@ -40,7 +40,8 @@ int tcs_abi_version(void);                 /* bumped when a signature changes (7
                                               10: tcs_conv2d_group_fused; 11: the *_mixed entry points;
                                               12: tcs_convex_upsample_pair, tcs_resize_bilinear_scaled; 13: the tcs_*loss* entry points;
                                               14: tcs_corr_lookup_backward, tcs_corr_build_backward*;
-                                              15: tcs_loss_finish_counts, the tcs_*loss*_bwd entry points) */
+                                              15: tcs_loss_finish_counts, the tcs_*loss*_bwd entry points;
+                                              16: tcs_upsample_flow*, tcs_convex_upsample*_backward*, tcs_refine_blend*) */
 const char* tcs_error_string(int code);
 
 /* ------------------------------------------------------------------------------------------------
@@ -657,6 +658,36 @@ int tcs_grad_normal_loss_bwd(const float* grad_preds, long long grad_stride, con
                              const float* norm_gt, const uint8_t* norm_mask, const uint8_t* norm_valid, int B, int H, int W,
                              const double* loss_weights, const double* counts, const float* upstream, float* grad_grad_preds,
                              float* grad_q_preds, tcs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Differentiable convex upsampling and propagate-blend (tcs_mi355/train_ops.py).  The forwards take the
+ * reference's own arguments; the backwards recompute the softmax from the saved inputs, write every wanted output element exactly
+ * once (zeros included; no memset, no float atomics: two calls are bit-equal) and read nothing on the host.  A NULL gradient
+ * output means "not wanted".
+ * ---------------------------------------------------------------------------------------------- */
+/* TCStereo.upsample_flow(flow, mask, scale=True) at factor 4 (tc_stereo.py:75-88): flow [B,1,H,W], mask [B,144,H,W] ->
+ * flow_up [B,1,4H,4W], bit-equal to tcs_convex_upsample(disp = -flow, clip = 0). */
+int tcs_upsample_flow(const float* flow, const float* mask, int B, int H, int W, float* flow_up, tcs_stream_t stream);
+/* both upsamplings of one iteration (tc_stereo.py:213-214) on one shared mask: bit-equal to tcs_convex_upsample_pair(-flow_a, -flow_b) */
+int tcs_upsample_flow_pair(const float* flow_a, const float* flow_b, const float* mask, int B, int H, int W, float* up_a, float* up_b,
+                           tcs_stream_t stream);
+/* floats of the caller-owned workspace of the two backwards below when n_flows (0, 1 or 2) flow gradients are wanted */
+size_t tcs_convex_upsample_backward_workspace_floats(int B, int H, int W, int n_flows);
+/* grad_up [B,1,4H,4W] (16-byte aligned) -> grad_mask [B,144,H,W] and grad_flow [B,1,H,W]; flow is read for grad_mask only and may be
+ * NULL without it.  One launch; a wanted grad_flow adds the workspace's fixed-order 9-term gather as a second, small one. */
+int tcs_convex_upsample_backward(const float* flow, const float* mask, const float* grad_up, int B, int H, int W, float* grad_mask,
+                                 float* grad_flow, float* workspace, tcs_stream_t stream);
+/* the pair's: the mask was detached in output a, so grad_mask comes from flow_b and grad_up_b alone and is bit-equal to
+ * tcs_convex_upsample_backward(flow_b, mask, grad_up_b)'s; an upstream gradient that no wanted output reads may be NULL */
+int tcs_convex_upsample_pair_backward(const float* flow_b, const float* mask, const float* grad_up_a, const float* grad_up_b, int B, int H,
+                                      int W, float* grad_mask, float* grad_flow_a, float* grad_flow_b, float* workspace, tcs_stream_t stream);
+/* update.py:294,298-300 in one launch: refined [B,1,H,W] = sum_k softmax(logits9 - max)_k * cand_k(disp_grads, disp), the candidates
+ * of tcs_propagate_disparity formed in registers; bit-equal to tcs_softmax_blend on tcs_propagate_disparity's output. */
+int tcs_refine_blend(const float* logits9, const float* disp_grads, const float* disp, int B, int H, int W, float* refined,
+                     tcs_stream_t stream);
+/* grad_refined [B,1,H,W] -> grad_logits [B,9,H,W], grad_disp_grads [B,2,H,W]; disp gets no gradient (the reference detaches it) */
+int tcs_refine_blend_backward(const float* logits9, const float* disp_grads, const float* disp, const float* grad_refined, int B, int H,
+                              int W, float* grad_logits, float* grad_disp_grads, tcs_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -187,7 +187,9 @@ __global__ __launch_bounds__(256) void k_softmax_blend(const float* __restrict__
     }
 }
 
-// tc_stereo.py:75-88 (factor 4) on flow = -disp, clipped like the returned dict (tc_stereo.py:223-224)
+// tc_stereo.py:75-88 (factor 4) on flow = -disp, clipped like the returned dict (tc_stereo.py:223-224).  FLOW: the first argument is
+// the flow itself (train_ops.upsample_flow): 4 * f for 4 * (-d), the same operations otherwise, and no flow_q
+template <bool FLOW>
 __global__ __launch_bounds__(256) void k_convex_upsample(const float* __restrict__ disp, const float* __restrict__ mask, int H, int W,
                                                          int clip, float* __restrict__ up, float* __restrict__ flow_q) {
     const int b = blockIdx.y, HW = H * W;
@@ -208,11 +210,11 @@ __global__ __launch_bounds__(256) void k_convex_upsample(const float* __restrict
 #pragma unroll
     for (int k = 0; k < 9; ++k) {
         const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
-        const float f = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? 4.f * (-d[yy * W + xx]) : 0.f;
+        const float f = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? 4.f * (FLOW ? d[yy * W + xx] : -d[yy * W + xx]) : 0.f;
         r += (w[k] / s) * f;
     }
     up[(size_t)b * Hu * Wu + pu] = clip ? fminf(r, 0.f) : r;
-    if (flow_q && i == 0 && j == 0) {
+    if (!FLOW && flow_q && i == 0 && j == 0) {
         const float fq = -d[y * W + x];
         flow_q[(size_t)b * HW + y * W + x] = clip ? fminf(fq, 0.f) : fq;
     }
@@ -221,6 +223,8 @@ __global__ __launch_bounds__(256) void k_convex_upsample(const float* __restrict
 // The convex upsampling of TWO disparities with the same mask (tc_stereo.py:204-215: flows_up of -disp_q and flow_refine_up of
 // -refined_disp share the iteration's up_mask): the 9 mask logits of an output pixel are read and soft-maxed once for both.  Unclipped,
 // and each output is bit-equal to k_convex_upsample(clip=0) on that disparity: the same loads and the same operations in the same order.
+// FLOW as in k_convex_upsample (train_ops.upsample_flow_pair; q_a, q_b unused).
+template <bool FLOW>
 __global__ __launch_bounds__(256) void k_convex_upsample_pair(const float* __restrict__ disp_a, const float* __restrict__ disp_b,
                                                               const float* __restrict__ mask, int H, int W, float* __restrict__ up_a,
                                                               float* __restrict__ up_b, float* __restrict__ q_a, float* __restrict__ q_b) {
@@ -244,15 +248,15 @@ __global__ __launch_bounds__(256) void k_convex_upsample_pair(const float* __res
     for (int k = 0; k < 9; ++k) {
         const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
         const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
-        const float fa = in ? 4.f * (-da[yy * W + xx]) : 0.f;
-        const float fb = in ? 4.f * (-db[yy * W + xx]) : 0.f;
+        const float fa = in ? 4.f * (FLOW ? da[yy * W + xx] : -da[yy * W + xx]) : 0.f;
+        const float fb = in ? 4.f * (FLOW ? db[yy * W + xx] : -db[yy * W + xx]) : 0.f;
         const float wk = w[k] / s;
         ra += wk * fa;
         rb += wk * fb;
     }
     up_a[(size_t)b * Hu * Wu + pu] = ra;
     up_b[(size_t)b * Hu * Wu + pu] = rb;
-    if (i == 0 && j == 0) {
+    if (!FLOW && i == 0 && j == 0) {
         q_a[(size_t)b * HW + y * W + x] = -da[y * W + x];
         q_b[(size_t)b * HW + y * W + x] = -db[y * W + x];
     }
@@ -419,6 +423,228 @@ __global__ __launch_bounds__(256) void k_pack_tap_weights(const float* __restric
     packed[u] = *reinterpret_cast<uint4*>(&v);
 }
 
+// =====================================================================================================================
+// Training ops (tcs_mi355/train_ops.py): the backward of the convex upsampling and DispRefine's blend as one
+// forward launch, with its backward.  No float atomics, every output element written once (zeros included), sums in a fixed order.
+// =====================================================================================================================
+// Backward of k_convex_upsample<true> / k_convex_upsample_pair<true>.  With s_k the softmax of the 9 logits of output pixel
+// (4y+i, 4x+j), f_k the zero-padded neighbour of 4 * flow and up = sum_k s_k f_k:
+//   dmask[k*16+i*4+j][y][x] = s_k (f_k - up) g_b                        (the pair's mask gradient comes from flow_b's output only)
+//   ws_x[k][y][x]           = sum_{i,j} s_k g_x                          (x = a, b: what centre (y,x) sends to its neighbour k)
+// and k_upsample_flow_bwd_gather sums the <= 9 centres that have a pixel as in-image neighbour.  A workgroup is 64 consecutive
+// low-resolution pixels x the 4 sub-rows i (one wave each): a thread reads its 4 x 9 logits (each load 256 contiguous bytes per
+// wave), its four upstream gradients as one 16-byte load, and writes 36 mask gradients the same way; the four waves' partials meet
+// in LDS and are added in the order i = 0..3.  Any of g_a / ws_a, g_b / ws_b, dmask may be null (not wanted); flow is read for
+// dmask only.
+__global__ __launch_bounds__(256) void k_upsample_flow_bwd(const float* __restrict__ flow, const float* __restrict__ mask,
+                                                           const float* __restrict__ g_a, const float* __restrict__ g_b, int H, int W,
+                                                           float* __restrict__ dmask, float* __restrict__ ws_a, float* __restrict__ ws_b) {
+    __shared__ float sp[4][18][64];
+    const int b = blockIdx.y, HW = H * W;
+    const int lane = threadIdx.x & 63, i = threadIdx.x >> 6;
+    const int p = blockIdx.x * 64 + lane;
+    float pa[9], pb[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) pa[k] = pb[k] = 0.f;
+    if (p < HW) {
+        const int y = p / W, x = p - y * W;
+        float f[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
+            f[k] = (dmask && yy >= 0 && yy < H && xx >= 0 && xx < W) ? 4.f * flow[(size_t)b * HW + yy * W + xx] : 0.f;
+        }
+        const size_t go = (size_t)b * 16 * HW + (size_t)(4 * y + i) * (4 * W) + 4 * x;        // 16-byte aligned
+        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 ga4 = g_a ? *reinterpret_cast<const float4*>(g_a + go) : z4;
+        const float4 gb4 = g_b ? *reinterpret_cast<const float4*>(g_b + go) : z4;
+        const float ga[4] = {ga4.x, ga4.y, ga4.z, ga4.w}, gb[4] = {gb4.x, gb4.y, gb4.z, gb4.w};
+        const float* mk = mask + ((size_t)b * 144 + i * 4) * HW + p;
+        float w[4][9];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) w[j][k] = mk[(size_t)(k * 16 + j) * HW];
+        }
+        float* dm = dmask ? dmask + ((size_t)b * 144 + i * 4) * HW + p : nullptr;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float m = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) m = fmaxf(m, w[j][k]);
+            float s = 0.f;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) { w[j][k] = expf(w[j][k] - m); s += w[j][k]; }
+            // f_k - up cancels: up is summed in double (9 fp64 FMAs, free in a kernel bound by its 288 mask-sized bytes per pixel), so
+            // the difference carries the rounding of s_k alone and not that of a float32 sum of magnitude |flow|
+            double up = 0.0;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) { w[j][k] = w[j][k] / s; up += (double)w[j][k] * (double)f[k]; }
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                pa[k] += w[j][k] * ga[j];
+                pb[k] += w[j][k] * gb[j];
+                if (dm) dm[(size_t)(k * 16 + j) * HW] = w[j][k] * (float)((double)f[k] - up) * gb[j];
+            }
+        }
+    }
+    if (!ws_a && !ws_b) return;                       // the same for every thread
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { sp[i][k][lane] = pa[k]; sp[i][9 + k][lane] = pb[k]; }
+    __syncthreads();
+    for (int e = threadIdx.x; e < 18 * 64; e += 256) {
+        const int q = e >> 6, l = e & 63, pp = blockIdx.x * 64 + l;
+        float* dst = q < 9 ? ws_a : ws_b;
+        if (pp < HW && dst) dst[((size_t)b * 9 + (q < 9 ? q : q - 9)) * HW + pp] = ((sp[0][q][l] + sp[1][q][l]) + sp[2][q][l]) + sp[3][q][l];
+    }
+}
+
+// dflow[y'][x'] = 4 * sum_k ws[k][centre], centre = (y' - (k/3 - 1), x' - (k%3 - 1)) where it lies in the image, k = 0..8 in order.
+// blockIdx.z selects flow a or b; a null output is skipped.
+__global__ __launch_bounds__(256) void k_upsample_flow_bwd_gather(const float* __restrict__ ws_a, const float* __restrict__ ws_b, int H, int W,
+                                                                  float* __restrict__ dflow_a, float* __restrict__ dflow_b) {
+    const float* ws = blockIdx.z ? ws_b : ws_a;
+    float* out = blockIdx.z ? dflow_b : dflow_a;
+    if (!out) return;
+    const int b = blockIdx.y, HW = H * W;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= HW) return;
+    const int y = p / W, x = p - y * W;
+    float t[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const int cy = y - (k / 3 - 1), cx = x - (k % 3 - 1);
+        const bool in = cy >= 0 && cy < H && cx >= 0 && cx < W;
+        const float v = ws[((size_t)b * 9 + k) * HW + min(max(cy, 0), H - 1) * W + min(max(cx, 0), W - 1)];
+        t[k] = in ? v : 0.f;
+    }
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) acc += t[k];
+    out[(size_t)b * HW + p] = 4.f * acc;
+}
+
+// update.py:294,298-300 as one launch: the 9 candidates of k_propagate formed in registers, then the blend of k_softmax_blend; the
+// same operations in the same order as those two kernels, so `refined` is bit-equal to theirs
+__global__ __launch_bounds__(256) void k_refine_blend(const float* __restrict__ logits, const float* __restrict__ grad,
+                                                      const float* __restrict__ disp, int H, int W, float* __restrict__ refined) {
+    const int b = blockIdx.y, HW = H * W;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= HW) return;
+    const int y = p / W, x = p - y * W;
+    const float* d = disp + (size_t)b * HW;
+    const float* gx = grad + (size_t)b * 2 * HW;
+    const float* gy = gx + HW;
+    const float* l = logits + (size_t)b * 9 * HW + p;
+    float c[9];
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            const int yy = y + v - 1, xx = x + u - 1;
+            const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
+            const int q = min(max(yy, 0), H - 1) * W + min(max(xx, 0), W - 1);
+            const float dn = d[q];                              // replicate pad
+            const float gnx = in ? gx[q] : 0.f;                 // zero pad
+            const float gny = in ? gy[q] : 0.f;
+            c[3 * v + u] = dn + gnx * (float)(1 - u) + gny * (float)(1 - v);
+        }
+    }
+    float w[9], m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { w[k] = l[(size_t)k * HW]; m = fmaxf(m, w[k]); }
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { w[k] = expf(w[k] - m); s += w[k]; }
+    // k_softmax_blend's `r += (w[k] / s) * cand` compiles to one fused multiply-add per term; with the candidates in registers the
+    // compiler would pack the products two by two and round them before the sum, so the fused form is spelled out
+    float r = 0.f;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) r = __builtin_fmaf(w[k] / s, c[k], r);
+    refined[(size_t)b * HW + p] = r;
+}
+
+// Backward of k_refine_blend, one launch.  With s_k the softmax of centre c's logits and g its upstream gradient:
+//   dlogits[k][c]  = s_k (cand_k - refined) g
+//   dgrad[0][n]    = sum over the centres c that have n as in-image neighbour k = 3v+u of s_k(c) g(c) (1-u);   dgrad[1][n]: (1-v)
+// A workgroup owns a 32 x 8 tile: t_k = s_k g of the tile's centres and of a one-pixel halo of centres (softmax recomputed: 9 logits
+// each) goes to LDS, zero for a centre outside the image; then each pixel gathers its 9 terms in the order k = 0..8.  disp, replicate-
+// padded, gets no gradient.  dlogits / dgrad may be null (not wanted).
+#define RB_TX 32
+#define RB_TY 8
+#define RB_SX (RB_TX + 2)
+#define RB_SY (RB_TY + 2)
+__global__ __launch_bounds__(256) void k_refine_blend_bwd(const float* __restrict__ logits, const float* __restrict__ grad,
+                                                          const float* __restrict__ disp, const float* __restrict__ g, int H, int W,
+                                                          float* __restrict__ dlogits, float* __restrict__ dgrad) {
+    __shared__ float st[9][RB_SY * RB_SX];
+    const int b = blockIdx.z, HW = H * W;
+    const int tx0 = blockIdx.x * RB_TX, ty0 = blockIdx.y * RB_TY;
+    const float* d = disp + (size_t)b * HW;
+    const float* gx = grad + (size_t)b * 2 * HW;
+    const float* gy = gx + HW;
+    for (int e = threadIdx.x; e < RB_SY * RB_SX; e += 256) {
+        const int ey = e / RB_SX, ex = e - ey * RB_SX;
+        const int cy = ty0 + ey - 1, cx = tx0 + ex - 1;
+        float t[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) t[k] = 0.f;
+        if (cy >= 0 && cy < H && cx >= 0 && cx < W) {
+            const int p = cy * W + cx;
+            const float* l = logits + (size_t)b * 9 * HW + p;
+            float w[9], m = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) { w[k] = l[(size_t)k * HW]; m = fmaxf(m, w[k]); }
+            float s = 0.f;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) { w[k] = expf(w[k] - m); s += w[k]; }
+            const float gg = g[(size_t)b * HW + p];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) { w[k] = w[k] / s; t[k] = w[k] * gg; }
+            if (dlogits && ey >= 1 && ey <= RB_TY && ex >= 1 && ex <= RB_TX) {
+                float c[9];
+                double r = 0.0;                       // cand_k - refined cancels: the sum in double, as in k_upsample_flow_bwd
+#pragma unroll
+                for (int v = 0; v < 3; ++v) {
+#pragma unroll
+                    for (int u = 0; u < 3; ++u) {
+                        const int yy = cy + v - 1, xx = cx + u - 1;
+                        const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
+                        const int q = min(max(yy, 0), H - 1) * W + min(max(xx, 0), W - 1);
+                        const float dn = d[q];
+                        const float gnx = in ? gx[q] : 0.f;
+                        const float gny = in ? gy[q] : 0.f;
+                        c[3 * v + u] = dn + gnx * (float)(1 - u) + gny * (float)(1 - v);
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < 9; ++k) r += (double)w[k] * (double)c[k];
+#pragma unroll
+                for (int k = 0; k < 9; ++k) dlogits[((size_t)b * 9 + k) * HW + p] = w[k] * (float)((double)c[k] - r) * gg;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) st[k][e] = t[k];
+    }
+    if (!dgrad) return;                               // the same for every thread
+    __syncthreads();
+    const int ly = threadIdx.x / RB_TX, lx = threadIdx.x - ly * RB_TX;
+    const int y = ty0 + ly, x = tx0 + lx;
+    if (y >= H || x >= W) return;
+    float ax = 0.f, ay = 0.f;
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            const float t = st[3 * v + u][(ly + 2 - v) * RB_SX + (lx + 2 - u)];     // centre = pixel - (v-1, u-1)
+            ax += t * (float)(1 - u);
+            ay += t * (float)(1 - v);
+        }
+    }
+    dgrad[((size_t)b * 2 + 0) * HW + y * W + x] = ax;
+    dgrad[((size_t)b * 2 + 1) * HW + y * W + x] = ay;
+}
+
 extern "C" {
 
 size_t tcs_tap_weights_floats(int nout, int C) {
@@ -513,7 +739,7 @@ int tcs_softmax_blend_s16(const float* logits9, const float* cand, int cand_ctot
 int tcs_convex_upsample(const float* disp, const float* mask, int B, int H, int W, int clip, float* flow_up, float* flow_q,
                         tcs_stream_t stream) {
     if (!disp || !mask || !flow_up || B <= 0 || B > 65535 || H <= 0 || W <= 0) return TCS_EINVAL;
-    hipLaunchKernelGGL(k_convex_upsample, dim3(tcs_cdiv((long long)16 * H * W, 256), B), dim3(256), 0, tcs_stream(stream),
+    hipLaunchKernelGGL(k_convex_upsample<false>, dim3(tcs_cdiv((long long)16 * H * W, 256), B), dim3(256), 0, tcs_stream(stream),
                        disp, mask, H, W, clip, flow_up, flow_q);
     return tcs_launch_status();
 }
@@ -522,7 +748,7 @@ int tcs_convex_upsample_pair(const float* disp_a, const float* disp_b, const flo
                              float* q_a, float* q_b, tcs_stream_t stream) {
     if (!disp_a || !disp_b || !mask || !up_a || !up_b || !q_a || !q_b || B <= 0 || B > 65535 || H <= 0 || W <= 0) return TCS_EINVAL;
     if ((long long)16 * H * W > 0x7fffffffLL) return TCS_EUNSUPPORTED;
-    hipLaunchKernelGGL(k_convex_upsample_pair, dim3(tcs_cdiv((long long)16 * H * W, 256), B), dim3(256), 0, tcs_stream(stream),
+    hipLaunchKernelGGL(k_convex_upsample_pair<false>, dim3(tcs_cdiv((long long)16 * H * W, 256), B), dim3(256), 0, tcs_stream(stream),
                        disp_a, disp_b, mask, H, W, up_a, up_b, q_a, q_b);
     return tcs_launch_status();
 }
@@ -535,7 +761,73 @@ int tcs_avgpool3s2(const float* x, int B, int C, int H, int W, float* out, tcs_s
     return tcs_launch_status();
 }
 
-int tcs_abi_version(void) { return 15; }
+// ---- training ops ----
+static bool tcs_up_shape_ok(int B, int H, int W) { return B > 0 && B <= 65535 && H > 0 && W > 0 && (long long)16 * H * W <= 0x7fffffffLL; }
+
+int tcs_upsample_flow(const float* flow, const float* mask, int B, int H, int W, float* flow_up, tcs_stream_t stream) {
+    if (!flow || !mask || !flow_up || B <= 0 || H <= 0 || W <= 0) return TCS_EINVAL;
+    if (!tcs_up_shape_ok(B, H, W)) return TCS_EUNSUPPORTED;
+    hipLaunchKernelGGL(k_convex_upsample<true>, dim3(tcs_cdiv((long long)16 * H * W, 256), B), dim3(256), 0, tcs_stream(stream),
+                       flow, mask, H, W, 0, flow_up, (float*)nullptr);
+    return tcs_launch_status();
+}
+
+int tcs_upsample_flow_pair(const float* flow_a, const float* flow_b, const float* mask, int B, int H, int W, float* up_a, float* up_b,
+                           tcs_stream_t stream) {
+    if (!flow_a || !flow_b || !mask || !up_a || !up_b || B <= 0 || H <= 0 || W <= 0) return TCS_EINVAL;
+    if (!tcs_up_shape_ok(B, H, W)) return TCS_EUNSUPPORTED;
+    hipLaunchKernelGGL(k_convex_upsample_pair<true>, dim3(tcs_cdiv((long long)16 * H * W, 256), B), dim3(256), 0, tcs_stream(stream),
+                       flow_a, flow_b, mask, H, W, up_a, up_b, (float*)nullptr, (float*)nullptr);
+    return tcs_launch_status();
+}
+
+size_t tcs_convex_upsample_backward_workspace_floats(int B, int H, int W, int n_flows) {
+    if (B <= 0 || H <= 0 || W <= 0 || n_flows < 0 || n_flows > 2) return 0;
+    return (size_t)n_flows * 9 * B * H * W;
+}
+
+int tcs_convex_upsample_pair_backward(const float* flow_b, const float* mask, const float* grad_up_a, const float* grad_up_b, int B, int H,
+                                      int W, float* grad_mask, float* grad_flow_a, float* grad_flow_b, float* workspace, tcs_stream_t stream) {
+    if (!mask || B <= 0 || H <= 0 || W <= 0 || (!grad_mask && !grad_flow_a && !grad_flow_b)) return TCS_EINVAL;
+    if ((grad_mask && (!flow_b || !grad_up_b)) || (grad_flow_a && !grad_up_a) || (grad_flow_b && !grad_up_b)) return TCS_EINVAL;
+    if ((grad_flow_a || grad_flow_b) && !workspace) return TCS_EINVAL;
+    if (((uintptr_t)grad_up_a | (uintptr_t)grad_up_b) & 15) return TCS_EINVAL;
+    if (!tcs_up_shape_ok(B, H, W)) return TCS_EUNSUPPORTED;
+    const size_t plane = (size_t)9 * B * H * W;
+    float* ws_a = grad_flow_a ? workspace : nullptr;
+    float* ws_b = grad_flow_b ? workspace + (grad_flow_a ? plane : 0) : nullptr;
+    hipLaunchKernelGGL(k_upsample_flow_bwd, dim3(tcs_cdiv((long long)H * W, 64), B), dim3(256), 0, tcs_stream(stream), flow_b, mask,
+                       grad_flow_a ? grad_up_a : nullptr, (grad_mask || grad_flow_b) ? grad_up_b : nullptr, H, W, grad_mask, ws_a, ws_b);
+    if (grad_flow_a || grad_flow_b)
+        hipLaunchKernelGGL(k_upsample_flow_bwd_gather, dim3(tcs_cdiv((long long)H * W, 256), B, 2), dim3(256), 0, tcs_stream(stream),
+                           ws_a, ws_b, H, W, grad_flow_a, grad_flow_b);
+    return tcs_launch_status();
+}
+
+int tcs_convex_upsample_backward(const float* flow, const float* mask, const float* grad_up, int B, int H, int W, float* grad_mask,
+                                 float* grad_flow, float* workspace, tcs_stream_t stream) {
+    return tcs_convex_upsample_pair_backward(flow, mask, nullptr, grad_up, B, H, W, grad_mask, nullptr, grad_flow, workspace, stream);
+}
+
+int tcs_refine_blend(const float* logits9, const float* disp_grads, const float* disp, int B, int H, int W, float* refined,
+                     tcs_stream_t stream) {
+    if (!logits9 || !disp_grads || !disp || !refined || B <= 0 || B > 65535 || H <= 0 || W <= 0) return TCS_EINVAL;
+    hipLaunchKernelGGL(k_refine_blend, dim3(tcs_cdiv((long long)H * W, 256), B), dim3(256), 0, tcs_stream(stream), logits9, disp_grads,
+                       disp, H, W, refined);
+    return tcs_launch_status();
+}
+
+int tcs_refine_blend_backward(const float* logits9, const float* disp_grads, const float* disp, const float* grad_refined, int B, int H,
+                              int W, float* grad_logits, float* grad_disp_grads, tcs_stream_t stream) {
+    if (!logits9 || !grad_refined || B <= 0 || B > 65535 || H <= 0 || W <= 0 || (!grad_logits && !grad_disp_grads)) return TCS_EINVAL;
+    if (grad_logits && (!disp_grads || !disp)) return TCS_EINVAL;
+    if (tcs_cdiv(H, RB_TY) > 65535) return TCS_EUNSUPPORTED;
+    hipLaunchKernelGGL(k_refine_blend_bwd, dim3(tcs_cdiv(W, RB_TX), tcs_cdiv(H, RB_TY), B), dim3(256), 0, tcs_stream(stream), logits9,
+                       disp_grads, disp, grad_refined, H, W, grad_logits, grad_disp_grads);
+    return tcs_launch_status();
+}
+
+int tcs_abi_version(void) { return 16; }
 
 const char* tcs_error_string(int code) {
     switch (code) {

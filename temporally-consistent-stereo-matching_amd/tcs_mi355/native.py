@@ -160,6 +160,13 @@ SIGNATURES = {
     "tcs_init_loss_bwd": (c_int, [c_fp, c_int, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_f, c_fp, c_fp, c_fp, c_fp]),
     "tcs_grad_normal_loss_bwd": (c_int, [c_fp, C.c_longlong, c_fp, C.c_longlong, C.c_longlong, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
                                          c_int, c_int, c_int, C.POINTER(C.c_double), c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "tcs_upsample_flow": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp]),
+    "tcs_upsample_flow_pair": (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp]),
+    "tcs_convex_upsample_backward_workspace_floats": (c_sz, [c_int, c_int, c_int, c_int]),
+    "tcs_convex_upsample_backward": (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp]),
+    "tcs_convex_upsample_pair_backward": (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "tcs_refine_blend": (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp]),
+    "tcs_refine_blend_backward": (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp]),
 }
 
 

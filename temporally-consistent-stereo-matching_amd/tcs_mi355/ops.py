@@ -413,6 +413,114 @@ def convex_upsample_pair(disp_a, disp_b, mask, up_a=None, up_b=None, q_a=None, q
     return tuple(outs)
 
 
+# ---------------------------------------------------------------------------------------------
+# training ops: raw launches (tcs_mi355/train_ops.py holds the autograd surface)
+# ---------------------------------------------------------------------------------------------
+def _flow_mask_dims(flow, mask, name="flow"):
+    B, D, H, W = _dims4(flow, name)
+    if D != 1:
+        raise ValueError(f"{name} must be [B,1,H,W], got {tuple(flow.shape)}")
+    if tuple(mask.shape) != (B, 144, H, W):
+        raise ValueError(f"mask must be [B,144,H,W] (factor 4) for a {name} of shape {tuple(flow.shape)}, got {tuple(mask.shape)}")
+    return B, H, W
+
+
+def upsample_flow(flow, mask):
+    """TCStereo.upsample_flow(flow, mask, scale=True) at factor 4 -> [B,1,4H,4W]; bit-equal to convex_upsample(-flow, mask, clip=False)[0]."""
+    B, H, W = _flow_mask_dims(flow, mask)
+    up = _new(flow, B, 1, 4 * H, 4 * W)
+    nv.check(nv.lib().tcs_upsample_flow(nv.ptr(flow, "flow"), nv.ptr(mask, "mask"), B, H, W, nv.ptr(up), nv.stream()), "tcs_upsample_flow")
+    return up
+
+
+def upsample_flow_pair(flow_a, flow_b, mask):
+    """Both upsamplings of one iteration in one launch -> (up_a, up_b); bit-equal to convex_upsample_pair(-flow_a, -flow_b, mask)[:2]."""
+    B, H, W = _flow_mask_dims(flow_a, mask, "flow_a")
+    _flow_mask_dims(flow_b, mask, "flow_b")
+    up_a, up_b = _new(flow_a, B, 1, 4 * H, 4 * W), _new(flow_a, B, 1, 4 * H, 4 * W)
+    nv.check(nv.lib().tcs_upsample_flow_pair(nv.ptr(flow_a, "flow_a"), nv.ptr(flow_b, "flow_b"), nv.ptr(mask, "mask"), B, H, W,
+                                             nv.ptr(up_a), nv.ptr(up_b), nv.stream()), "tcs_upsample_flow_pair")
+    return up_a, up_b
+
+
+def _grad16(g, shape, name):
+    """An upstream gradient as the kernels read it: float32, contiguous, 16-byte aligned."""
+    if tuple(g.shape) != shape:
+        raise ValueError(f"{name} must be {shape}, got {tuple(g.shape)}")
+    g = g.to(torch.float32).contiguous()
+    return g.clone() if g.data_ptr() % 16 else g
+
+
+def convex_upsample_pair_backward(flow_b, mask, grad_up_a, grad_up_b, want_mask=True, want_flow_a=True, want_flow_b=True):
+    """Backward of upsample_flow_pair -> (grad_mask, grad_flow_a, grad_flow_b), None where not wanted (nothing is allocated for it).
+    grad_mask comes from flow_b's output alone.  grad_up_a = None with want_flow_a=False is upsample_flow's backward."""
+    B, H, W = _flow_mask_dims(flow_b, mask, "flow_b")
+    if not (want_mask or want_flow_a or want_flow_b):
+        return None, None, None
+    shape = (B, 1, 4 * H, 4 * W)
+    ga = _grad16(grad_up_a, shape, "grad_up_a") if want_flow_a else None
+    gb = _grad16(grad_up_b, shape, "grad_up_b") if (want_mask or want_flow_b) else None
+    g_mask = _new(mask, B, 144, H, W) if want_mask else None
+    g_a = _new(mask, B, 1, H, W) if want_flow_a else None
+    g_b = _new(mask, B, 1, H, W) if want_flow_b else None
+    n = int(want_flow_a) + int(want_flow_b)
+    ws = _new(mask, int(nv.lib().tcs_convex_upsample_backward_workspace_floats(B, H, W, n))) if n else None
+    nv.check(nv.lib().tcs_convex_upsample_pair_backward(nv.ptr(flow_b, "flow_b"), nv.ptr(mask, "mask"), nv.ptr(ga), nv.ptr(gb), B, H, W,
+                                                        nv.ptr(g_mask), nv.ptr(g_a), nv.ptr(g_b), nv.ptr(ws), nv.stream()),
+             "tcs_convex_upsample_pair_backward")
+    return g_mask, g_a, g_b
+
+
+def convex_upsample_backward(flow, mask, grad_up, want_mask=True, want_flow=True):
+    """Backward of upsample_flow -> (grad_mask, grad_flow), None where not wanted."""
+    B, H, W = _flow_mask_dims(flow, mask)
+    if not (want_mask or want_flow):
+        return None, None
+    g = _grad16(grad_up, (B, 1, 4 * H, 4 * W), "grad_up")
+    g_mask = _new(mask, B, 144, H, W) if want_mask else None
+    g_flow = _new(mask, B, 1, H, W) if want_flow else None
+    ws = _new(mask, int(nv.lib().tcs_convex_upsample_backward_workspace_floats(B, H, W, 1))) if want_flow else None
+    nv.check(nv.lib().tcs_convex_upsample_backward(nv.ptr(flow, "flow"), nv.ptr(mask, "mask"), nv.ptr(g), B, H, W, nv.ptr(g_mask),
+                                                   nv.ptr(g_flow), nv.ptr(ws), nv.stream()), "tcs_convex_upsample_backward")
+    return g_mask, g_flow
+
+
+def _blend_dims(logits, disp_grads, disp):
+    B, C, H, W = _dims4(logits, "logits")
+    if C != 9:
+        raise ValueError(f"logits must be [B,9,H,W], got {tuple(logits.shape)}")
+    if tuple(disp_grads.shape) != (B, 2, H, W):
+        raise ValueError(f"disp_grads must be {(B, 2, H, W)}, got {tuple(disp_grads.shape)}")
+    if tuple(disp.shape) != (B, 1, H, W):
+        raise ValueError(f"disp must be {(B, 1, H, W)}, got {tuple(disp.shape)}")
+    return B, H, W
+
+
+def refine_blend(logits, disp_grads, disp):
+    """sum_k softmax(logits - max)_k * cand_k(disp_grads, disp) -> [B,1,H,W]; bit-equal to
+    softmax_blend(logits, propagate_disparity(disp_grads, disp))[0], the candidates never written."""
+    B, H, W = _blend_dims(logits, disp_grads, disp)
+    refined = _new(logits, B, 1, H, W)
+    nv.check(nv.lib().tcs_refine_blend(nv.ptr(logits, "logits"), nv.ptr(disp_grads, "disp_grads"), nv.ptr(disp, "disp"), B, H, W,
+                                       nv.ptr(refined), nv.stream()), "tcs_refine_blend")
+    return refined
+
+
+def refine_blend_backward(logits, disp_grads, disp, grad_refined, want_logits=True, want_grads=True):
+    """Backward of refine_blend -> (grad_logits, grad_disp_grads), None where not wanted."""
+    B, H, W = _blend_dims(logits, disp_grads, disp)
+    if not (want_logits or want_grads):
+        return None, None
+    if tuple(grad_refined.shape) != (B, 1, H, W):
+        raise ValueError(f"grad_refined must be {(B, 1, H, W)}, got {tuple(grad_refined.shape)}")
+    g = grad_refined.to(torch.float32).contiguous()
+    g_l = _new(logits, B, 9, H, W) if want_logits else None
+    g_g = _new(logits, B, 2, H, W) if want_grads else None
+    nv.check(nv.lib().tcs_refine_blend_backward(nv.ptr(logits, "logits"), nv.ptr(disp_grads, "disp_grads"), nv.ptr(disp, "disp"), nv.ptr(g),
+                                                B, H, W, nv.ptr(g_l), nv.ptr(g_g), nv.stream()), "tcs_refine_blend_backward")
+    return g_l, g_g
+
+
 def avgpool3s2(x, out=None):
     B, Cc, H, W = _dims4(x, "x")
     out = _new(x, B, Cc, (H - 1) // 2 + 1, (W - 1) // 2 + 1) if out is None else out
