@@ -41,7 +41,8 @@ int tcs_abi_version(void);                 /* bumped when a signature changes (7
                                               12: tcs_convex_upsample_pair, tcs_resize_bilinear_scaled; 13: the tcs_*loss* entry points;
                                               14: tcs_corr_lookup_backward, tcs_corr_build_backward*;
                                               15: tcs_loss_finish_counts, the tcs_*loss*_bwd entry points;
-                                              16: tcs_upsample_flow*, tcs_convex_upsample*_backward*, tcs_refine_blend*) */
+                                              16: tcs_upsample_flow*, tcs_convex_upsample*_backward*, tcs_refine_blend*;
+                                              17: tcs_conv2d_s16_plan) */
 const char* tcs_error_string(int code);
 
 /* ------------------------------------------------------------------------------------------------
@@ -570,6 +571,18 @@ int tcs_conv2d_s16(const tcs_conv_s16_desc* desc, tcs_stream_t stream);
  * descriptors would run as one launch (no launch is made). */
 int tcs_conv2d_s16_group(const tcs_conv_s16_desc* const* descs, int n, tcs_stream_t stream);
 int tcs_conv2d_s16_group_fused(const tcs_conv_s16_desc* const* descs, int n);
+
+/* The tile instance tcs_conv2d_s16 would launch for a descriptor: the kernel's template parameters (ksize, stride, epilogue, cout tiles of
+ * 32 per workgroup `mt`, output rows per workgroup `rows`, 16-channel k-steps per stage `ksteps`, LDS stages `nstage`, `row_split` and
+ * `rows_per_wave` of the tile code's fifth digit, `taps` = 1 for the tap-partial instances), the MFMA products per k-step (a descriptor
+ * that says 0 reports 3), the block -> XCD mapping digit `csplit` as the launch would use it, and the launch geometry (`blocks` per batch
+ * element, `threads` = 64 * rows / rows_per_wave, dynamic LDS).  With tile_cfg = 0 this is the heuristic's choice.  Launches nothing and
+ * dereferences no tensor pointer, so it also answers on a machine without a GPU.  Returns what tcs_conv2d_s16 would return before its
+ * launch (TCS_OK, TCS_EINVAL, TCS_EUNSUPPORTED); `out` is written on TCS_OK only.  The tests take the library's instance table and the
+ * instances of the model's layers from here instead of restating launch_s16_cfg / s16_heuristic (tests/s16_instances.py). */
+typedef struct tcs_s16_instance { int ksize, stride, epilogue, mt, rows, ksteps, nstage, row_split, rows_per_wave, taps,
+                                  products, csplit, blocks, threads; long long lds_bytes; } tcs_s16_instance;
+int tcs_conv2d_s16_plan(const tcs_conv_s16_desc* desc, tcs_s16_instance* out);
 
 /* ------------------------------------------------------------------------------------------------
  * The training objective (train_stereo.py:41-180, 362-399): targets, the four losses, metrics

@@ -1152,6 +1152,35 @@ int tcs_conv2d_s16_group_fused(const tcs_conv_s16_desc* const* descs, int n) {
            (a == k1422 && b == k3411);
 }
 
+int tcs_conv2d_s16_plan(const tcs_conv_s16_desc* desc, tcs_s16_instance* out) {
+    // the planner of the grouped launches, exported: tests read the instance table and the heuristic's choices from the library
+    if (!desc || !out) return TCS_EINVAL;
+    S16Plan plan;
+    plan.filled = false;
+    g_s16_plan = &plan;
+    const int rc = tcs_conv2d_s16(desc, nullptr);
+    g_s16_plan = nullptr;
+    if (rc != TCS_OK) return rc;
+    if (!plan.filled) return TCS_EINVAL;
+    long long k = plan.key;                         // s16_key(): ((KS MT ROWS KSTEPS NSTAGE STRIDE EPI RS RPW) base 10) * 2 + TP
+    out->taps = (int)(k & 1); k >>= 1;
+    out->rows_per_wave = (int)(k % 10); k /= 10;
+    out->row_split = (int)(k % 10); k /= 10;
+    out->epilogue = (int)(k % 10); k /= 10;
+    out->stride = (int)(k % 10); k /= 10;
+    out->nstage = (int)(k % 10); k /= 10;
+    out->ksteps = (int)(k % 10); k /= 10;
+    out->rows = (int)(k % 10); k /= 10;
+    out->mt = (int)(k % 10); k /= 10;
+    out->ksize = (int)k;
+    out->products = plan.nprod;
+    out->csplit = plan.args.csplit;
+    out->blocks = plan.nblocks;
+    out->threads = plan.threads;
+    out->lds_bytes = (long long)plan.lds;
+    return TCS_OK;
+}
+
 }  // extern "C"
 
 // this translation unit's S16 domain flag (tcs_s16.h): read-and-clear for tcs_s16_flags()

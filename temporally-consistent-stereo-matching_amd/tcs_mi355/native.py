@@ -64,6 +64,12 @@ class ConvS16Desc(C.Structure):
     ]
 
 
+class S16Instance(C.Structure):
+    """struct tcs_s16_instance (include/tcs_mi355.h): what tcs_conv2d_s16_plan reports."""
+    _fields_ = [(n, c_int) for n in ("ksize", "stride", "epilogue", "mt", "rows", "ksteps", "nstage", "row_split", "rows_per_wave", "taps",
+                                     "products", "csplit", "blocks", "threads")] + [("lds_bytes", C.c_longlong)]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/tcs_mi355.h
 SIGNATURES = {
     "tcs_abi_version": (c_int, []),
@@ -128,6 +134,7 @@ SIGNATURES = {
     "tcs_conv2d_s16": (c_int, [C.POINTER(ConvS16Desc), c_fp]),
     "tcs_conv2d_s16_group": (c_int, [C.POINTER(C.POINTER(ConvS16Desc)), c_int, c_fp]),
     "tcs_conv2d_s16_group_fused": (c_int, [C.POINTER(C.POINTER(ConvS16Desc)), c_int]),
+    "tcs_conv2d_s16_plan": (c_int, [C.POINTER(ConvS16Desc), C.POINTER(S16Instance)]),
     "tcs_avgpool3s2_s16": (c_int, [c_fp, c_int, c_int, c_int, c_int, c_fp, c_int, c_fp]),
     "tcs_resize_bilinear_s16": (c_int, [c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_int, c_fp]),
     "tcs_instance_norm_s16_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),

@@ -17,6 +17,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import s16_instances as si
 from conftest import T, epe, maxdiff
 
 pytestmark = pytest.mark.gpu
@@ -89,8 +90,7 @@ def test_conv2d_s16_single_product(dev, cfg):
     S = F.conv2d(r16(x).abs(), rw(w, pc).abs(), b.double().abs(), padding=pad, stride=stride)
     K = cin * k * k
     xs16 = [s16.to_s16(D(x_, dev)) for x_ in xs]
-    tiles = [0] + ([1411, 1812, 21812, 11412 + 1000] if k == 3 and stride == 1 and cfg["cout"] % 64 == 0 else
-                   [1411, 1812, 21812] if k == 3 and stride == 1 else [])
+    tiles = [0] + si.linear_tiles(k, stride, cfg["cins"], cfg["cout"])       # every instance of the table (tests/s16_instances.py) for this layer
     for tc in tiles:
         _, o32 = s16.conv2d(pc, xs16, want32=True, stride=stride, tile_cfg=tc)
         check(o32, ref16, ref32, K, S, (cfg, tc))

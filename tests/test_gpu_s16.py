@@ -9,6 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import s16_instances as si
 from conftest import maxdiff
 
 pytestmark = pytest.mark.gpu
@@ -77,21 +78,10 @@ def test_conv2d_s16_vs_torch(dev, cfg):
     add = torch.randn(ref.shape, generator=gen)
     pc = ops.pack_conv(D(w, dev), D(b, dev), "f16x3")
     xs16 = [s16.to_s16(D(x, dev)) for x in xs]
-    tiles = [0]
-    # every tile configuration the library instantiates (launch_s16_cfg): MT*1000 + ROWS*100 + KSTEPS*10 + NSTAGE, +10000 row split,
-    # +100000*CSPLIT block -> XCD mapping; 64-channel tiles (MT = 2) need an even number of 32-channel tiles
-    if cfg["k"] == 3 and stride == 1:
-        tiles += [1411, 1412, 1413, 1811, 1512, 101812, 201412]
-        tiles += [21812, 21412, 21411, 121812]                          # two rows per wave (RS digit 2)
-        tiles += [2411, 2412, 2413, 2512, 102812, 12412, 12413, 22812, 22412, 122812] if cfg["cout"] % 64 == 0 else []
-    elif cfg["k"] == 1 and stride == 1:
-        ksteps = [(c + 15) // 16 for c in cfg["cins"]]
-        tiles += [1412]
-        for kst in (2, 4):
-            if all(k % kst == 0 for k in ksteps):
-                tiles += [1400 + 10 * kst + 2, 101400 + 10 * kst + 2] + ([1423] if kst == 2 else [])
-                tiles += ([2400 + 10 * kst + 2] + ([2423] if kst == 2 else [])) if cfg["cout"] % 64 == 0 else []
-        tiles += [2412] if cfg["cout"] % 64 == 0 else []
+    # every tile configuration the library instantiates for this kind of layer, from the table that test_s16_instances_host.py holds
+    # against launch_s16_cfg (tests/s16_instances.py), each with both block -> XCD mappings, + CSPLIT = 2 once
+    tiles = [0] + si.linear_tiles(cfg["k"], stride, cfg["cins"], cfg["cout"], csplit_too=True)
+    tiles += [201412] if cfg["k"] == 3 and stride == 1 else []
     for tc in tiles:
         o16, o32 = s16.conv2d(pc, xs16, want32=True, stride=stride, tile_cfg=tc)
         assert maxdiff(o32, ref) <= 2e-5, tc
@@ -441,6 +431,10 @@ def test_grouped_launch_equals_separate_launches(dev):
         ((96, 96, 3, 120, 160), 0, (96, 96, 1, 120, 160), 0, True),                # context_compress[2] | disp_f_stem[2]
         ((192, 96, 3, 120, 160), 101411, (27, 96, 1, 120, 160), 0, True),          # ... with the 4-row single-stage 3x3 tile the loop uses
         ((64, 64, 3, 9, 33), 101411, (64, 64, 3, 9, 33), 101412, False),           # no pair kernel for this combination: two launches
+        # batch 3 on ragged grids whose first half has a block count that is not a multiple of 8 (n0pad of launch_s16_pair: the blocks
+        # in between exit at once): 2 x 3 patches x 2 tiles = 12 -> 16, and 3 x 2 patches x 3 tiles = 18 -> 24
+        ((64, 64, 3, 9, 37, 3), 101412, (64, 64, 3, 9, 37, 3), 101412, True),
+        ((192, 96, 3, 11, 70, 3), 101812, (27, 96, 1, 11, 70, 3), 101422, True),
     ]
     for la, ta, lb, tb, fused in cases:
         xa, wa, ba, xa16, pca = layer(*la)
