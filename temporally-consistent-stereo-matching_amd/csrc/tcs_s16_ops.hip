@@ -63,9 +63,9 @@ __global__ __launch_bounds__(256) void k_resize_bilinear_s16(const _Float16* __r
 // InstanceNorm2d (affine=False, biased variance) + activation + optional S16 addend on an S16 tensor, two launches:
 //   k_in_stats_s16: grid (slices, B*G).  A block reduces its slice of the plane for the 8 channels of its group with the
 //       plane slice held in registers: sum -> slice mean -> sum of squares AROUND that mean (the reference's two-pass
-//       variance, not E[x^2] - mean^2), and writes (mean_i, M2_i) per channel.
+//       variance, not E[x^2] - mean^2) and sum of the deviations, which corrects the mean; writes (mean_i, M2_i) per channel.
 //   k_in_apply_s16: one thread per unit; every thread merges the partials of its (b, group) with Chan's pairwise formula
-//       (M2 = M2_a + M2_b + d^2 n_a n_b / n), then normalises its unit.
+//       (M2 = M2_a + M2_b + d^2 n_a n_b / n), the merged mean as a (mean, correction) pair, then normalises its unit.
 // A per-(b, channel) block like the fp32 kernel would leave a 64-channel tensor with 8 workgroups on 256 CUs.
 // ---------------------------------------------------------------------------------------------------------------------
 #define INS_T 256
@@ -109,16 +109,26 @@ __global__ __launch_bounds__(INS_T) void k_in_stats_s16(const _Float16* __restri
         for (int j = 0; j < 8; ++j) { v[k][j] = ok ? v[k][j] : 0.f; sum[j] += v[k][j]; }
     }
     block_sum8(sum, red);
-    float mean[8], m2[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float mean[8], m2[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, e[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < 8; ++j) mean[j] = sum[j] / (float)n;
 #pragma unroll
     for (int k = 0; k < INS_UPT; ++k) {
         const bool ok = p_lo + threadIdx.x + INS_T * k < p_hi;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { const float d = ok ? v[k][j] - mean[j] : 0.f; m2[j] = fmaf(d, d, m2[j]); }
+        for (int j = 0; j < 8; ++j) { const float d = ok ? v[k][j] - mean[j] : 0.f; m2[j] = fmaf(d, d, m2[j]); e[j] += d; }
     }
     block_sum8(m2, red);
+    // the deviations from the fp32 mean also sum to the first pass's error (k_instance_norm's corrected two-pass, tcs_conv_f16.hip): on a
+    // plane at an offset the fp32 sum of ~2,000 values loses what the normalised output needs (offset 8, sigma 0.5: 1.7e-6 against fp64
+    // where the fp32-tensor kernel has 4e-7); the deviations are small numbers and sum accurately
+    block_sum8(e, red);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float dm = e[j] / (float)n;
+        mean[j] += dm;
+        m2[j] = fmaxf(m2[j] - dm * e[j], 0.f);
+    }
     if (threadIdx.x < 8) {
         float* o = partial + ((size_t)bg * nsl + sl) * 16;
         o[threadIdx.x] = mean[threadIdx.x];
@@ -153,9 +163,11 @@ __global__ __launch_bounds__(INS_T) void k_in_apply_s16(const _Float16* __restri
     if (addend) s16_load8(addend + (((size_t)b * Ga + g) * 2) * plane + u, plane, t);
     // merge the slices' (n_i, mean_i, M2_i) pairwise (Chan et al.): the loads do not depend on the running sums, so they
     // are all in flight together; every lane reads the same addresses (one L2 transaction per wave-load)
-    float n = 0.f, mean[8], m2[8];
+    // the merged mean is the pair mean + mc: one fp32 number holds a mean of 8 to half an ulp = 4.8e-7 only, which the normalised
+    // output of a plane at an offset shows; mc collects what each update's addition rounds away (TwoSum, kept from contraction)
+    float n = 0.f, mean[8], mc[8], m2[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { mean[j] = 0.f; m2[j] = 0.f; }
+    for (int j = 0; j < 8; ++j) { mean[j] = 0.f; mc[j] = 0.f; m2[j] = 0.f; }
 #pragma unroll 4
     for (int i = 0; i < nsl; ++i) {
         const float4* pi = reinterpret_cast<const float4*>(partial + ((size_t)bg * nsl + i) * 16);
@@ -164,8 +176,10 @@ __global__ __launch_bounds__(INS_T) void k_in_apply_s16(const _Float16* __restri
         const float ni = (float)(min(HW, (i + 1) * slice_px) - i * slice_px), tot = n + ni, f = ni / tot;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float d = pm[j] - mean[j];
-            mean[j] += d * f;
+            const float d = (pm[j] - mean[j]) - mc[j];
+            const float upd = __fmul_rn(d, f), nm = __fadd_rn(mean[j], upd), bb = __fsub_rn(nm, mean[j]);
+            mc[j] += __fadd_rn(__fsub_rn(mean[j], __fsub_rn(nm, bb)), __fsub_rn(upd, bb));
+            mean[j] = nm;
             m2[j] += p2[j] + d * d * n * f;
         }
         n = tot;
@@ -174,7 +188,7 @@ __global__ __launch_bounds__(INS_T) void k_in_apply_s16(const _Float16* __restri
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const float rstd = 1.0f / sqrtf(m2[j] / (float)HW + eps);
-        v[j] = s16_act((v[j] - mean[j]) * rstd, act) + (addend ? t[j] : 0.f);
+        v[j] = s16_act(((v[j] - mean[j]) - mc[j]) * rstd, act) + (addend ? t[j] : 0.f);
         if (act == TCS_ACT_RELU_ADD_RELU) v[j] = fmaxf(v[j], 0.f);       // relu(relu(norm(x)) + skip), extractor.py:44-58
     }
     s16_store8(out + (((size_t)b * Go + g) * 2) * plane + u, plane, v);
