@@ -42,7 +42,8 @@ int tcs_abi_version(void);                 /* bumped when a signature changes (7
                                               14: tcs_corr_lookup_backward, tcs_corr_build_backward*;
                                               15: tcs_loss_finish_counts, the tcs_*loss*_bwd entry points;
                                               16: tcs_upsample_flow*, tcs_convex_upsample*_backward*, tcs_refine_blend*;
-                                              17: tcs_conv2d_s16_plan) */
+                                              17: tcs_conv2d_s16_plan;
+                                              18: tcs_gru_reset*, tcs_gru_update*) */
 const char* tcs_error_string(int code);
 
 /* ------------------------------------------------------------------------------------------------
@@ -701,6 +702,37 @@ int tcs_refine_blend(const float* logits9, const float* disp_grads, const float*
 /* grad_refined [B,1,H,W] -> grad_logits [B,9,H,W], grad_disp_grads [B,2,H,W]; disp gets no gradient (the reference detaches it) */
 int tcs_refine_blend_backward(const float* logits9, const float* disp_grads, const float* disp, const float* grad_refined, int B, int H,
                               int W, float* grad_logits, float* grad_disp_grads, tcs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Differentiable gate stages of the recurrent cells (tcs_mi355/train_ops.py): what ConvGRU (update.py:81-85),
+ * Lightfuse (:30-34) and HiddenstateUpdater (:62-66) do around their second convolution, one launch each.  All tensors are
+ * [B,C,H,W] float32 with contiguous planes and contiguous channels; every INPUT has its own batch stride in elements (>= C*H*W), so
+ * chunk / split views along the channels of a wider tensor are read in place.  Outputs, upstream gradients and gradients are
+ * contiguous.  Context terms (cr, cz, cq) may be NULL = zero.  16-byte accesses are used when C*H*W, every batch stride and every
+ * base address are multiples of 16 bytes, 4-byte accesses otherwise.  The backwards recompute the gates from the inputs and write
+ * every wanted output element exactly once (no memset, no atomics: two calls are bit-equal); a NULL gradient output means "not
+ * wanted", and the gradient of a context term IS the gradient of its pre-activation.  A NULL required pointer, a batch stride
+ * below C*H*W, a non-positive size or no wanted gradient is TCS_EINVAL before any HIP call.
+ * ---------------------------------------------------------------------------------------------- */
+/* rh = sigmoid(r_pre + cr) * h */
+int tcs_gru_reset(const float* r_pre, long long r_pre_stride, const float* h, long long h_stride, const float* cr, long long cr_stride,
+                  int B, int C, int H, int W, float* rh, tcs_stream_t stream);
+/* grad_r_pre (= d cr) = g h r (1 - r), grad_h = g r; h is read for grad_r_pre only and may be NULL without it */
+int tcs_gru_reset_backward(const float* r_pre, long long r_pre_stride, const float* h, long long h_stride, const float* cr,
+                           long long cr_stride, const float* grad_rh, int B, int C, int H, int W, float* grad_r_pre, float* grad_h,
+                           tcs_stream_t stream);
+/* z = sigmoid(z_pre + cz), q = tanh(q_pre + cq); h_new = (1 - z) h + z q (z_keeps_h = 0, ConvGRU) or z h + (1 - z) q (z_keeps_h != 0,
+ * Lightfuse and HiddenstateUpdater) */
+int tcs_gru_update(const float* z_pre, long long z_pre_stride, const float* q_pre, long long q_pre_stride, const float* h,
+                   long long h_stride, const float* cz, long long cz_stride, const float* cq, long long cq_stride, int z_keeps_h, int B,
+                   int C, int H, int W, float* h_new, tcs_stream_t stream);
+/* z_keeps_h = 0: grad_q_pre (= d cq) = g z (1 - q^2), grad_z_pre (= d cz) = g (q - h) z (1 - z), grad_h = g (1 - z); z_keeps_h != 0: z and
+ * 1 - z change places in grad_q_pre and grad_h, and grad_z_pre changes sign.  q_pre and cq are read for grad_z_pre and grad_q_pre only,
+ * h for grad_z_pre only; they may be NULL otherwise */
+int tcs_gru_update_backward(const float* z_pre, long long z_pre_stride, const float* q_pre, long long q_pre_stride, const float* h,
+                            long long h_stride, const float* cz, long long cz_stride, const float* cq, long long cq_stride,
+                            const float* grad_h_new, int z_keeps_h, int B, int C, int H, int W, float* grad_z_pre, float* grad_q_pre,
+                            float* grad_h, tcs_stream_t stream);
 
 #ifdef __cplusplus
 }

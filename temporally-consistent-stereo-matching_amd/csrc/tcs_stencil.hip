@@ -827,7 +827,7 @@ int tcs_refine_blend_backward(const float* logits9, const float* disp_grads, con
     return tcs_launch_status();
 }
 
-int tcs_abi_version(void) { return 17; }
+int tcs_abi_version(void) { return 18; }
 
 const char* tcs_error_string(int code) {
     switch (code) {

@@ -21,6 +21,7 @@ c_fp = C.c_void_p      # device float*
 c_int = C.c_int
 c_f = C.c_float
 c_sz = C.c_size_t
+c_ll = C.c_longlong
 
 
 class ConvDesc(C.Structure):
@@ -174,6 +175,11 @@ SIGNATURES = {
     "tcs_convex_upsample_pair_backward": (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "tcs_refine_blend": (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp]),
     "tcs_refine_blend_backward": (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp]),
+    "tcs_gru_reset": (c_int, [c_fp, c_ll, c_fp, c_ll, c_fp, c_ll, c_int, c_int, c_int, c_int, c_fp, c_fp]),
+    "tcs_gru_reset_backward": (c_int, [c_fp, c_ll, c_fp, c_ll, c_fp, c_ll, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp]),
+    "tcs_gru_update": (c_int, [c_fp, c_ll, c_fp, c_ll, c_fp, c_ll, c_fp, c_ll, c_fp, c_ll, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp]),
+    "tcs_gru_update_backward": (c_int, [c_fp, c_ll, c_fp, c_ll, c_fp, c_ll, c_fp, c_ll, c_fp, c_ll, c_fp, c_int, c_int, c_int, c_int, c_int,
+                                        c_fp, c_fp, c_fp, c_fp]),
 }
 
 

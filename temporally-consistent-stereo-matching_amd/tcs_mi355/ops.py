@@ -521,6 +521,95 @@ def refine_blend_backward(logits, disp_grads, disp, grad_refined, want_logits=Tr
     return g_l, g_g
 
 
+def gate_view_ok(t) -> bool:
+    """Whether the gate kernels read `t` [B,C,H,W] in place: contiguous planes, contiguous channels within a batch element, and a batch
+    stride that steps over a whole element (what `chunk` / `split` along dim 1 of a contiguous tensor give)."""
+    B, C, H, W = t.shape
+    sb, sc, sh, sw = t.stride()
+    inner = (W == 1 or sw == 1) and (H == 1 or sh == W) and (C == 1 or sc == H * W)
+    return inner and (B == 1 or sb >= C * H * W)
+
+
+def _gate_dims(first, first_name, **others):
+    """[B,C,H,W] of the first tensor; ValueError unless every other one (None allowed) has the same shape."""
+    shape = _dims4(first, first_name)
+    for name, t in others.items():
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape} like {first_name}, got {tuple(t.shape)}")
+    return shape
+
+
+def _gate_in(t, name):
+    """(tensor that owns the memory, device pointer, batch stride in elements) of one gate input; None -> (None, NULL, 0)."""
+    if t is None:
+        return None, None, 0
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: tcs_mi355 kernels need a HIP device tensor, got device={t.device} "
+                           f"(there is no CPU path; use the oracle only for checking)")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name}: expected torch.float32, got {t.dtype}")
+    if not gate_view_ok(t):
+        t = t.contiguous()
+    B, C, H, W = t.shape
+    return t, t.data_ptr(), (int(t.stride(0)) if B > 1 else C * H * W)
+
+
+def _gate_grad(g, shape, name):
+    if tuple(g.shape) != shape:
+        raise ValueError(f"{name} must be {shape}, got {tuple(g.shape)}")
+    return g.to(torch.float32).contiguous()
+
+
+def gate_reset(r_pre, h, cr=None):
+    """sigmoid(r_pre + cr) * h -> rh [B,C,H,W] contiguous float32, one launch.  Inputs are read in place where gate_view_ok."""
+    B, C, H, W = _gate_dims(r_pre, "r_pre", h=h, cr=cr)
+    (k0, p_r, s_r), (k1, p_h, s_h), (k2, p_c, s_c) = _gate_in(r_pre, "r_pre"), _gate_in(h, "h"), _gate_in(cr, "cr")
+    rh = _new(r_pre, B, C, H, W)
+    nv.check(nv.lib().tcs_gru_reset(p_r, s_r, p_h, s_h, p_c, s_c, B, C, H, W, nv.ptr(rh), nv.stream()), "tcs_gru_reset")
+    return rh
+
+
+def gate_reset_backward(r_pre, h, cr, grad_rh, want_pre=True, want_h=True):
+    """Backward of gate_reset -> (grad_r_pre, grad_h), None where not wanted; grad_r_pre is also the gradient of cr."""
+    shape = _gate_dims(r_pre, "r_pre", h=h, cr=cr)
+    if not (want_pre or want_h):
+        return None, None
+    B, C, H, W = shape
+    (k0, p_r, s_r), (k1, p_h, s_h), (k2, p_c, s_c) = _gate_in(r_pre, "r_pre"), _gate_in(h, "h"), _gate_in(cr, "cr")
+    g = _gate_grad(grad_rh, shape, "grad_rh")
+    g_pre = _new(r_pre, *shape) if want_pre else None
+    g_h = _new(r_pre, *shape) if want_h else None
+    nv.check(nv.lib().tcs_gru_reset_backward(p_r, s_r, p_h, s_h, p_c, s_c, nv.ptr(g, "grad_rh"), B, C, H, W, nv.ptr(g_pre), nv.ptr(g_h),
+                                             nv.stream()), "tcs_gru_reset_backward")
+    return g_pre, g_h
+
+
+def gate_update(z_pre, q_pre, h, cz=None, cq=None, *, z_keeps_h):
+    """z = sigmoid(z_pre + cz), q = tanh(q_pre + cq) -> (1 - z) h + z q, or z h + (1 - z) q with z_keeps_h; one launch."""
+    B, C, H, W = _gate_dims(z_pre, "z_pre", q_pre=q_pre, h=h, cz=cz, cq=cq)
+    ins = [_gate_in(t, n) for t, n in ((z_pre, "z_pre"), (q_pre, "q_pre"), (h, "h"), (cz, "cz"), (cq, "cq"))]
+    h_new = _new(z_pre, B, C, H, W)
+    nv.check(nv.lib().tcs_gru_update(*(a for _, p, s in ins for a in (p, s)), int(bool(z_keeps_h)), B, C, H, W, nv.ptr(h_new), nv.stream()),
+             "tcs_gru_update")
+    return h_new
+
+
+def gate_update_backward(z_pre, q_pre, h, cz, cq, grad_h_new, *, z_keeps_h, want_z=True, want_q=True, want_h=True):
+    """Backward of gate_update -> (grad_z_pre, grad_q_pre, grad_h), None where not wanted; grad_z_pre is also the gradient of cz and
+    grad_q_pre that of cq."""
+    shape = _gate_dims(z_pre, "z_pre", q_pre=q_pre, h=h, cz=cz, cq=cq)
+    if not (want_z or want_q or want_h):
+        return None, None, None
+    B, C, H, W = shape
+    ins = [_gate_in(t, n) for t, n in ((z_pre, "z_pre"), (q_pre, "q_pre"), (h, "h"), (cz, "cz"), (cq, "cq"))]
+    g = _gate_grad(grad_h_new, shape, "grad_h_new")
+    g_z, g_q, g_h = (_new(z_pre, *shape) if want else None for want in (want_z, want_q, want_h))
+    nv.check(nv.lib().tcs_gru_update_backward(*(a for _, p, s in ins for a in (p, s)), nv.ptr(g, "grad_h_new"), int(bool(z_keeps_h)),
+                                              B, C, H, W, nv.ptr(g_z), nv.ptr(g_q), nv.ptr(g_h), nv.stream()),
+             "tcs_gru_update_backward")
+    return g_z, g_q, g_h
+
+
 def avgpool3s2(x, out=None):
     B, Cc, H, W = _dims4(x, "x")
     out = _new(x, B, Cc, (H - 1) // 2 + 1, (W - 1) // 2 + 1) if out is None else out

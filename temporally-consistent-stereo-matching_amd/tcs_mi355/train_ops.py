@@ -18,6 +18,14 @@ backward raises.  Otherwise the call is the forward launch alone and no node is 
 differentiably and the outputs are float32.  `disp` gets no gradient (the reference detaches it): NotImplementedError if it
 requires one.  CPU tensors raise (there is no CPU path).  DESIGN.md section 16.
 
+`gru_reset(r_pre, h, cr)` and `gru_update(z_pre, q_pre, h, cz, cq, z_keeps_h=...)` are the gate arithmetic of the recurrent cells
+(update.py: ConvGRU :81-85, Lightfuse :30-34, HiddenstateUpdater :62-66) on either side of the cell's second convolution:
+`r = sigmoid(r_pre + cr); rh = r * h` and `z = sigmoid(z_pre + cz); q = tanh(q_pre + cq); h_new = (1 - z) h + z q` (ConvGRU,
+`z_keeps_h=False`) or `z h + (1 - z) q` (the other two, `z_keeps_h=True`; there is no default, the two differ only by the side z is
+on).  One launch forward, one backward; the nodes save their inputs (the `chunk` / `split` views they were given, read in place) and
+recompute z, r and q, and the gradient of a context term is the tensor of its pre-activation's gradient.
+`patch_reference_cells(core.update)` points the three cells at them.  DESIGN.md section 17.
+
 This module imports no `core` package: the reference's training script has its own on the path.
 """
 from __future__ import annotations
@@ -84,6 +92,69 @@ class _RefineBlend(torch.autograd.Function):
         return g_l, g_g, None
 
 
+class _GruReset(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, r_pre, h, cr):
+        ctx.save_for_backward(r_pre, h, cr)
+        return ops.gate_reset(r_pre, h, cr)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        r_pre, h, cr = ctx.saved_tensors
+        need_pre, need_h, need_cr = ctx.needs_input_grad
+        g_pre, g_h = ops.gate_reset_backward(r_pre, h, cr, g, want_pre=need_pre or need_cr, want_h=need_h)
+        return (g_pre if need_pre else None), g_h, (g_pre if need_cr else None)
+
+
+class _GruUpdate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z_pre, q_pre, h, cz, cq, z_keeps_h):
+        ctx.save_for_backward(z_pre, q_pre, h, cz, cq)
+        ctx.z_keeps_h = z_keeps_h
+        return ops.gate_update(z_pre, q_pre, h, cz, cq, z_keeps_h=z_keeps_h)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        z_pre, q_pre, h, cz, cq = ctx.saved_tensors
+        need_z, need_q, need_h, need_cz, need_cq = ctx.needs_input_grad[:5]
+        g_z, g_q, g_h = ops.gate_update_backward(z_pre, q_pre, h, cz, cq, g, z_keeps_h=ctx.z_keeps_h, want_z=need_z or need_cz,
+                                                want_q=need_q or need_cq, want_h=need_h)
+        return (g_z if need_z else None), (g_q if need_q else None), g_h, (g_z if need_cz else None), (g_q if need_cq else None), None
+
+
+def _planes(t):
+    """A gate input as the node saves it: float32 (cast differentiably), and in a layout the kernels read in place."""
+    if t is None:
+        return None
+    if t.ndim != 4:
+        raise ValueError(f"expected a 4-D NCHW tensor, got shape {tuple(t.shape)}")
+    t = t.float()
+    return t if ops.gate_view_ok(t) else t.contiguous()
+
+
+def gru_reset(r_pre: torch.Tensor, h: torch.Tensor, cr: torch.Tensor | None = None) -> torch.Tensor:
+    """sigmoid(r_pre + cr) * h, all [N,C,H,W] (cr None = zero) -> [N,C,H,W] contiguous float32."""
+    r_pre, h, cr = _planes(r_pre), _planes(h), _planes(cr)
+    if _wants_grad(r_pre, h, *(() if cr is None else (cr,))):
+        ops._gate_dims(r_pre, "r_pre", h=h, cr=cr)
+        return _GruReset.apply(r_pre, h, cr)
+    return ops.gate_reset(r_pre, h, cr)
+
+
+def gru_update(z_pre: torch.Tensor, q_pre: torch.Tensor, h: torch.Tensor, cz: torch.Tensor | None = None,
+               cq: torch.Tensor | None = None, *, z_keeps_h: bool) -> torch.Tensor:
+    """z = sigmoid(z_pre + cz), q = tanh(q_pre + cq); z_keeps_h=False: (1 - z) h + z q (ConvGRU); z_keeps_h=True: z h + (1 - z) q
+    (Lightfuse, HiddenstateUpdater).  All [N,C,H,W] (cz, cq None = zero) -> [N,C,H,W] contiguous float32."""
+    z_keeps_h = bool(z_keeps_h)
+    z_pre, q_pre, h, cz, cq = (_planes(t) for t in (z_pre, q_pre, h, cz, cq))
+    if _wants_grad(*(t for t in (z_pre, q_pre, h, cz, cq) if t is not None)):
+        ops._gate_dims(z_pre, "z_pre", q_pre=q_pre, h=h, cz=cz, cq=cq)
+        return _GruUpdate.apply(z_pre, q_pre, h, cz, cq, z_keeps_h)
+    return ops.gate_update(z_pre, q_pre, h, cz, cq, z_keeps_h=z_keeps_h)
+
+
 def upsample_flow(flow: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     """flow [N,1,H,W], mask [N,144,H,W] (channel k*16 + i*4 + j) -> [N,1,4H,4W] float32."""
     flow, mask = _f32(flow), _f32(mask)
@@ -140,4 +211,32 @@ def patch_reference(tc_stereo_module, update_module):
 
     def undo():
         TCStereo.upsample_flow, DispRefine.forward = originals
+    return undo
+
+
+def patch_reference_cells(update_module):
+    """Point the reference's recurrent cells at the gate ops: `ConvGRU.forward` (z_keeps_h=False), `Lightfuse.forward` and
+    `HiddenstateUpdater.forward` (z_keeps_h=True).  Each keeps the module's own convolutions and concatenations; the reference's NaN
+    asserts are dropped (they synchronise with the host).  Returns a function that undoes the patch."""
+    ConvGRU, Lightfuse, Updater = update_module.ConvGRU, update_module.Lightfuse, update_module.HiddenstateUpdater
+    originals = (ConvGRU.forward, Lightfuse.forward, Updater.forward)
+
+    def gru_forward(self, h, cz, cr, cq, *x_list):
+        x = torch.cat(x_list, dim=1)
+        z_pre, r_pre = self.convzr(torch.cat([h, x], dim=1)).chunk(2, dim=1)
+        q_pre = self.convq(torch.cat([gru_reset(r_pre, h, cr), x], dim=1))
+        return gru_update(z_pre, q_pre, h, cz, cq, z_keeps_h=False)
+
+    def fuse_forward(self, h, x):
+        z_pre, r_pre = self.convzr(torch.cat([h, x], dim=1)).chunk(2, dim=1)
+        q_pre = self.convq(torch.cat([gru_reset(r_pre, h), x], dim=1))
+        return gru_update(z_pre, q_pre, h, z_keeps_h=True)
+
+    def updater_forward(self, h, x):
+        return fuse_forward(self, h, self.convs(x))
+
+    ConvGRU.forward, Lightfuse.forward, Updater.forward = gru_forward, fuse_forward, updater_forward
+
+    def undo():
+        ConvGRU.forward, Lightfuse.forward, Updater.forward = originals
     return undo
